@@ -8,7 +8,9 @@ single-GPU config the metric is quoted on: 10k utf8 "sensor_{k}" keys
 cost the reference pays), 1s tumbling window, count/min/max/avg(reading)
 + filter(max > 113), f64 readings, synthetic sensor stream (seeded; spec in
 DESIGN.md §Generator). A step = one push of --rows-per-step rows through the
-operator (device-resident inputs) including triggered window emission; the
+operator (device-resident inputs) including triggered window emission. Runs
+too long to keep resident (--resident-gib) are timed in stretches, their
+inputs regenerated in place between them with the clock stopped. The
 default run covers 768M rows (≥ cfg2's 100M; longer runs amortize warmup so
 the steady state dominates). --key-kind dense measures the pre-densified
 int-key variant (round-1's headline).
@@ -23,8 +25,11 @@ is not in the timed path (each GPU owns its keys for the whole run). The only
 collective is the shared-watermark all-reduce (MAX), exchanged before each
 push. scaling=weak: per-rank rows fixed as N grows.
 
-Rank 0 prints ONE JSON line. cpu_baseline: the CPU oracle (kind "port") timed
-on this box's host cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line. A plain run does only what the headline figure
+needs: set up, warm up, time the K steps, print. --full adds cpu_baseline:
+the CPU oracle (kind "port") timed on this box's host cores on a bounded
+sample of the same workload. --dump-outputs DIR writes what the last timed
+step emitted (see dump_outputs) so two builds can be compared array by array.
 """
 import argparse
 import ctypes
@@ -78,7 +83,20 @@ def parse_args():
                    help="use the staging-copy push instead of the zero-copy "
                         "borrowed push (also the fallback for A/B runs "
                         "against engine builds without the borrowed entry)")
-    p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: the "
+                        "CPU oracle baseline (cpu_baseline in the result "
+                        "line); off by default so a plain run stays lean")
+    p.add_argument("--skip-cpu-baseline", action="store_true",
+                   help="with --full: leave cpu_baseline out again")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the batches the last "
+                        "timed step emitted as DIR/<name>.npy (float32/"
+                        "float64, at most 64 MB; a seeded row sample beyond)")
+    p.add_argument("--resident-gib", type=float, default=64.0,
+                   help="cap on the device-resident part of the input "
+                        "stream; a longer run regenerates its inputs in "
+                        "place, outside the timed stretches")
     p.add_argument("--debug-steps", action="store_true",
                    help="print per-step wall times (push / poll split) to stderr")
     p.add_argument("--cpu-sample-rows", type=int, default=8_000_000)
@@ -146,6 +164,69 @@ def read_traffic():
         return None
 
 
+GEN_THREADS = 8  # host threads preparing variable-length input columns
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload, well under the 64 MB cap
+
+
+def dump_outputs(dirname, batches, t_last, seed, rank, world):
+    """Write the last timed step's output as DIR/<name>.npy.
+
+    `batches` are owned copies of every batch polled from the last timed
+    push through finish()+drain(). Emission is pipelined, so windows closed
+    by EARLIER steps may also surface in those polls, depending on timing;
+    they are dropped here: only rows of windows ending after `t_last` (the
+    last step's first timestamp) are kept — no earlier step can have closed
+    those, so the dumped rows are the same from run to run. Columns are the
+    batch's own (key / key_offsets+key_data, the aggregates, valid,
+    window_start, window_end), concatenated in emission order, as float64
+    (float32 for the byte-valued ones; all values are exactly representable).
+    Above DUMP_BUDGET a seeded, sorted row sample is written instead."""
+    os.makedirs(dirname, exist_ok=True)
+    utf8 = bool(batches) and "key_offsets" in batches[0]
+    cols = {}
+    names = [k for k in (batches[0] if batches else {})
+             if k not in ("n_rows", "key_offsets", "key_data")]
+    keep = [b["window_end"] > t_last for b in batches]
+    for k in names:
+        cols[k] = (np.concatenate([b[k][m] for b, m in zip(batches, keep)])
+                   if batches else np.zeros(0))
+    n = int(sum(int(m.sum()) for m in keep))
+    if utf8:
+        starts = np.concatenate(
+            [b["key_offsets"][:-1][m].astype(np.int64) + base
+             for b, m, base in zip(
+                 batches, keep,
+                 np.cumsum([0] + [len(b["key_data"]) for b in batches])[:-1])])
+        lens = np.concatenate(
+            [np.diff(b["key_offsets"])[m].astype(np.int64)
+             for b, m in zip(batches, keep)])
+        data = np.concatenate([b["key_data"] for b in batches])
+    row_bytes = 8 * len(names) + ((8 + float(lens.mean()) * 4)
+                                  if utf8 and n else 0)
+    sampled = False
+    if n and n * row_bytes > DUMP_BUDGET:
+        take = int(DUMP_BUDGET // row_bytes)
+        idx = np.sort(np.random.default_rng(seed).choice(n, take,
+                                                         replace=False))
+        cols = {k: v[idx] for k, v in cols.items()}
+        cols["sample_row_index"] = idx
+        if utf8:
+            starts, lens = starts[idx], lens[idx]
+        n, sampled = take, True
+    if utf8:
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=offs[1:])
+        gather = (np.repeat(starts - offs[:-1], lens)
+                  + np.arange(int(offs[-1]), dtype=np.int64))
+        cols["key_offsets"] = offs
+        cols["key_data"] = data[gather]
+    suffix = f".rank{rank}" if world > 1 else ""
+    for k, v in cols.items():
+        dt = np.float32 if v.dtype.itemsize == 1 else np.float64
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v.astype(dt))
+    return n, sampled
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -170,29 +251,33 @@ def main():
         device = local_rank % max(1, torch.cuda.device_count())
     K, W = args.steps, args.warmup
     B = args.rows_per_step
-    total_rows = (K + W) * B
 
-    # pre-generate the whole stream into HBM (inputs resident when the timed
-    # region starts). Each rank owns a disjoint key shard (weak scaling):
-    # same time distribution, rank-distinct keys (ids are rank-local).
+    # The stream is generated into HBM before it is pushed (inputs resident
+    # when a timed step starts). Each rank owns a disjoint key shard (weak
+    # scaling): same time distribution, rank-distinct keys (ids are
+    # rank-local). The resident part is capped at --resident-gib: a run of up
+    # to C steps is generated whole, up front; a longer one is generated C
+    # steps at a time into the same buffers, with the clock stopped (see the
+    # step loop).
     if args.ingest and args.cfg5:
         raise SystemExit("--ingest and --cfg5 are separate workloads")
     utf8 = args.key_kind == "utf8" and not args.cfg5 and not args.ingest
     gseed = args.seed + 1000003 * rank  # rank-distinct draws per shard
-    d_ts = dz.DeviceArray(device, total_rows * 8)
-    d_kid = None if (utf8 or args.cfg5) else dz.DeviceArray(device,
-                                                            total_rows * 4)
+    key_max = 7 + len(str(max(0, args.keys - 1)))  # "sensor_{k}"
+    # {"occurred_at_ms":T,"sensor_name":"sensor_K","reading":III.FFFFFF}\n
+    json_max = (18 + len(str(1_000_000 + (K + W) * B // args.rows_per_ms))
+                + 16 + key_max + 12 + 3 + 1 + 6 + 2)
+    row_bytes = (20 + json_max if args.ingest else 24 if args.cfg5 else
+                 20 + key_max if utf8 else 20)
+    C = max(1, min(K + W, int(args.resident_gib * 2**30) // (B * row_bytes)))
+    d_ts = dz.DeviceArray(device, C * B * 8)
+    d_kid = None if (utf8 or args.cfg5) else dz.DeviceArray(device, C * B * 4)
     d_trips = join = None
     if args.cfg5:
         # probe stream: trip ids (int64) from the same seeded draw; build
         # side (trip -> driver) fully resident before the timed region
-        d_trips = dz.DeviceArray(device, total_rows * 8)
-    d_vals = dz.DeviceArray(device, total_rows * 8)
-    dz.generate(device, gseed, 1_000_000, 0, total_rows,
-                args.trips if args.cfg5 else args.keys,
-                args.rows_per_ms, d_ts.ptr,
-                d_trips.ptr if args.cfg5 else None,
-                d_kid.ptr if d_kid else None, d_vals.ptr)
+        d_trips = dz.DeviceArray(device, C * B * 8)
+    d_vals = dz.DeviceArray(device, C * B * 8)
     if args.cfg5:
         rng = np.random.default_rng(gseed)
         trips_h = np.arange(args.trips, dtype=np.int64)
@@ -205,70 +290,91 @@ def main():
         join.push_build(args.trips, d_btr.ptr, d_bdr.ptr)
         d_btr.free()
         d_bdr.free()
-    d_offs = d_data = None
-    decoder = None
-    json_base = []
-    if args.ingest:
-        # pre-generate the on-wire JSON stream into HBM, one slice per step
-        d_lens = dz.DeviceArray(device, B * 4)
-        d_joffs = dz.DeviceArray(device, (B + 1) * 8)
-        total_bytes = 0
-        step_lens = []
-        for s_ in range(K + W):
-            dz.generate_json(device, gseed, 1_000_000, s_ * B, B, args.keys,
-                             args.rows_per_ms, d_lens=d_lens.ptr)
-            lens = d_lens.to_host(np.int32, B)
-            json_base.append(total_bytes)
-            step_lens.append(lens)
-            total_bytes += int(lens.sum())
-        d_data = dz.DeviceArray(device, total_bytes)
+    d_data = d_offs = decoder = None
+    varlen = utf8 or args.ingest
+    row_max = json_max if args.ingest else key_max
+    slot_bytes = [0] * C  # byte length of each resident step's data slice
+    json_bytes_total = 0
+    scratch = None
+    if varlen:
+        # variable-length columns (utf8 keys / JSON records), per-step Arrow
+        # slices: lens pass on the device, host prefix sum into the step's
+        # offsets, device fill pass. Every step's slice sits at a fixed base
+        # (slot * B * row_max), so the steps are independent and a few host
+        # threads work on them side by side, each with scratch of its own
+        # (the prefix sum and the two copies release the GIL).
+        import queue
+        from concurrent.futures import ThreadPoolExecutor
         L = _lib.lib()
-        for s_ in range(K + W):
-            offs = np.zeros(B + 1, np.int64)
-            np.cumsum(step_lens[s_], out=offs[1:])
-            step_lens[s_] = int(offs[-1])  # slice byte length
-            d_joffs.from_host(offs)
-            dz.generate_json(device, gseed, 1_000_000, s_ * B, B, args.keys,
-                             args.rows_per_ms, d_offsets=d_joffs.ptr,
-                             d_data=ctypes.c_void_p(
-                                 d_data.ptr.value + json_base[s_]))
-        json_lens = step_lens
-        d_lens.free()
-        d_joffs.free()
-        decoder = dz.JsonDecoder(device=device)
-        json_bytes_total = total_bytes
-    step_data_base = []
-    if utf8:
-        # utf8 key column, per-step Arrow slices: lens on device, host cumsum
-        # into per-step int32 offsets, then the device fill pass. All
-        # pre-generation — the timed region starts with everything resident.
-        d_lens = dz.DeviceArray(device, B * 4)
-        d_offs = dz.DeviceArray(device, (K + W) * (B + 1) * 4)
-        host_offs = []
-        total_bytes = 0
-        for s in range(K + W):
-            dz.generate_utf8(device, gseed, s * B, B, args.keys,
-                             d_lens=d_lens.ptr)
-            lens = d_lens.to_host(np.int32, B)
-            o = np.zeros(B + 1, np.int32)
-            np.cumsum(lens, out=o[1:])
-            host_offs.append(o)
-            step_data_base.append(total_bytes)
-            total_bytes += int(o[-1])
-        d_data = dz.DeviceArray(device, total_bytes)
-        L = _lib.lib()
-        for s in range(K + W):
-            optr = ctypes.c_void_p(d_offs.ptr.value + s * (B + 1) * 4)
-            L.dz_memcpy_h2d(optr, host_offs[s].ctypes.data_as(ctypes.c_void_p),
-                            (B + 1) * 4)
-            host_offs[s] = None  # cap host memory at one step's offsets
-            dz.generate_utf8(device, gseed, s * B, B, args.keys,
-                             d_offsets=optr,
-                             d_key_data=ctypes.c_void_p(
-                                 d_data.ptr.value + step_data_base[s]))
-        d_lens.free()
-        del host_offs
-    dz.synchronize(device)
+        odt = np.int64 if args.ingest else np.int32
+        osz = np.dtype(odt).itemsize
+        d_data = dz.DeviceArray(device, C * B * row_max)
+        if utf8:
+            d_offs = dz.DeviceArray(device, C * (B + 1) * 4)
+        else:
+            decoder = dz.JsonDecoder(device=device)
+        n_workers = max(1, min(GEN_THREADS, C))
+        scratch = queue.SimpleQueue()
+        for _ in range(n_workers):
+            scratch.put({
+                "d_lens": dz.DeviceArray(device, B * 4),
+                "d_offs": (None if utf8 else
+                           dz.DeviceArray(device, (B + 1) * 8)),
+                "h_lens": np.empty(B, np.int32),
+                "h_offs": np.zeros(B + 1, odt),
+            })
+        gen_pool = ThreadPoolExecutor(n_workers)
+
+    def generate_slot(s_, slot):
+        sc = scratch.get()
+        try:
+            if utf8:
+                dz.generate_utf8(device, gseed, s_ * B, B, args.keys,
+                                 d_lens=sc["d_lens"].ptr)
+                offs_p = ctypes.c_void_p(d_offs.ptr.value + slot * (B + 1) * 4)
+            else:
+                dz.generate_json(device, gseed, 1_000_000, s_ * B, B,
+                                 args.keys, args.rows_per_ms,
+                                 d_lens=sc["d_lens"].ptr)
+                offs_p = sc["d_offs"].ptr
+            if L.dz_memcpy_d2h(sc["h_lens"].ctypes.data_as(ctypes.c_void_p),
+                               sc["d_lens"].ptr, B * 4) != _lib.DZ_OK:
+                raise RuntimeError("d2h failed")
+            np.cumsum(sc["h_lens"], out=sc["h_offs"][1:])  # [0] stays 0
+            nbytes = int(sc["h_offs"][-1])
+            if L.dz_memcpy_h2d(offs_p,
+                               sc["h_offs"].ctypes.data_as(ctypes.c_void_p),
+                               (B + 1) * osz) != _lib.DZ_OK:
+                raise RuntimeError("h2d failed")
+            data_p = ctypes.c_void_p(d_data.ptr.value + slot * B * row_max)
+            if utf8:
+                dz.generate_utf8(device, gseed, s_ * B, B, args.keys,
+                                 d_offsets=offs_p, d_key_data=data_p)
+            else:
+                dz.generate_json(device, gseed, 1_000_000, s_ * B, B,
+                                 args.keys, args.rows_per_ms,
+                                 d_offsets=offs_p, d_data=data_p)
+            return nbytes
+        finally:
+            scratch.put(sc)
+
+    def generate_steps(lo, hi):
+        """Stream steps [lo, hi) -> resident slots 0..hi-lo (hi - lo <= C)."""
+        nonlocal json_bytes_total
+        dz.generate(device, gseed, 1_000_000, lo * B, (hi - lo) * B,
+                    args.trips if args.cfg5 else args.keys,
+                    args.rows_per_ms, d_ts.ptr,
+                    d_trips.ptr if args.cfg5 else None,
+                    d_kid.ptr if d_kid else None, d_vals.ptr)
+        if varlen:
+            sizes = list(gen_pool.map(generate_slot, range(lo, hi),
+                                      range(hi - lo)))
+            slot_bytes[:hi - lo] = sizes
+            if args.ingest:
+                json_bytes_total += sum(sizes)
+        dz.synchronize(device)
+
+    generate_steps(0, min(C, K + W))
 
     op = dz.WindowOp(length_ms=args.window_ms, slide_ms=args.slide_ms,
                      aggs=[("count", 0), ("min", 0), ("max", 0), ("avg", 0)],
@@ -279,11 +385,13 @@ def main():
         op.set_filter("max", ">", 113.0)
 
     def do_push(step):
-        off = step * B
+        slot = step % C
+        off = slot * B
         if args.ingest:
             # on-wire bytes -> decode -> intern -> window, all on device
-            decoder.decode(ctypes.c_void_p(d_data.ptr.value + json_base[step]),
-                           json_lens[step])
+            decoder.decode(ctypes.c_void_p(d_data.ptr.value
+                                           + slot * B * row_max),
+                           slot_bytes[slot])
             nr, pts, pko, pkd, pv = decoder.batch()
             op.push_device_utf8(nr, pts, pko, pkd, pv)
             return
@@ -304,8 +412,8 @@ def main():
             op.push_device_utf8(
                 B,
                 ctypes.c_void_p(d_ts.ptr.value + off * 8),
-                ctypes.c_void_p(d_offs.ptr.value + step * (B + 1) * 4),
-                ctypes.c_void_p(d_data.ptr.value + step_data_base[step]),
+                ctypes.c_void_p(d_offs.ptr.value + slot * (B + 1) * 4),
+                ctypes.c_void_p(d_data.ptr.value + slot * B * row_max),
                 ctypes.c_void_p(d_vals.ptr.value + off * 8))
         else:
             op.push_device(B,
@@ -313,6 +421,14 @@ def main():
                            ctypes.c_void_p(d_kid.ptr.value + off * 4),
                            ctypes.c_void_p(d_vals.ptr.value + off * 8),
                            borrowed=not args.staged_push)
+
+    # --dump-outputs: owned copies of the batches polled from the last timed
+    # push onward (None = not collecting; the views die at the next poll)
+    kept = None
+
+    def own(b):
+        return {k: (np.array(v) if isinstance(v, np.ndarray) else v)
+                for k, v in b.items()}
 
     def push_step(step):
         if dist is not None:
@@ -341,47 +457,85 @@ def main():
         # as the reference's downstream operator would.
         for b in op.poll_iter(copy=False):
             emitted += b["n_rows"]
+            if kept is not None:
+                kept.append(own(b))
         return emitted
 
     emitted = 0
+    marks = []
+
+    def run_steps(lo, hi):
+        nonlocal emitted, kept
+        for s in range(lo, hi):
+            if args.dump_outputs and s == W + K - 1:
+                kept = []
+            if args.debug_steps and s >= W:
+                a = time.perf_counter()
+                do_push(s)
+                m = time.perf_counter()
+                for bt in op.poll_iter(copy=False):
+                    emitted += bt["n_rows"]
+                    if kept is not None:
+                        kept.append(own(bt))
+                marks.append((m - a, time.perf_counter() - m))
+            else:
+                emitted += push_step(s)
+
+    def settle(last):
+        """Bring everything pushed so far to completion: the end of the
+        timed region (last: finish() closes the open windows), or a stop
+        before the resident buffers are refilled (drain() processes the
+        deferred batch and ends its borrow of them)."""
+        nonlocal emitted
+        if last:
+            tf = time.perf_counter()
+            op.finish()
+            if args.debug_steps:
+                print(f"finish {(time.perf_counter()-tf)*1e3:.3f} ms",
+                      file=sys.stderr)
+        op.drain()
+        for b in op.poll_iter(copy=False):
+            emitted += b["n_rows"]
+            if kept is not None:
+                kept.append(own(b))
+        dz.synchronize(device)
+        if dist is not None:
+            dist.barrier()
+
     import gc
     gc.collect()
     gc.disable()  # a gen-0 pass every ~7 steps showed up as 1-2 ms stalls
-    for s in range(W):
-        emitted += push_step(s)
-    dz.synchronize(device)
-    if dist is not None:
-        dist.barrier()
-
-    t0 = time.perf_counter()
-    if args.debug_steps:
-        marks = []
-        for s in range(W, W + K):
-            a = time.perf_counter()
-            do_push(s)
-            m = time.perf_counter()
-            for bt in op.poll_iter(copy=False):
-                emitted += bt["n_rows"]
-            marks.append((m - a, time.perf_counter() - m))
-        tf = time.perf_counter()
-    else:
-        for s in range(W, W + K):
-            emitted += push_step(s)
-    op.finish()
-    if args.debug_steps:
-        print(f"finish {(time.perf_counter()-tf)*1e3:.3f} ms", file=sys.stderr)
-        for i, (pu, po) in enumerate(marks):
-            print(f"step {i} push {pu*1e3:7.3f} ms poll {po*1e3:7.3f} ms",
-                  file=sys.stderr)
-    op.drain()
-    emitted += sum(b["n_rows"] for b in op.poll_iter(copy=False))
-    dz.synchronize(device)
-    if dist is not None:
-        dist.barrier()
-    t1 = time.perf_counter()
+    # A run that fits the resident buffers (K + W <= C) is one stretch:
+    # warm up, synchronize, time the K steps through finish(). A longer one
+    # stops at every multiple of C steps: the stretch is settled with the
+    # clock running, the next C steps are generated with it stopped, and
+    # `elapsed` sums the timed stretches.
+    elapsed = 0.0
+    s = 0
+    while s < W + K:
+        if s and s % C == 0:
+            generate_steps(s, min(s + C, W + K))
+        hi = min(W + K, (s // C + 1) * C)
+        if s < W:
+            hi = min(hi, W)
+            run_steps(s, hi)
+            if hi % C == 0 and hi < W + K:
+                settle(False)
+            elif hi == W:
+                dz.synchronize(device)
+                if dist is not None:
+                    dist.barrier()
+        else:
+            t0 = time.perf_counter()
+            run_steps(s, hi)
+            settle(hi == W + K)
+            elapsed += time.perf_counter() - t0
+        s = hi
     gc.enable()
+    for i, (pu, po) in enumerate(marks):
+        print(f"step {i} push {pu*1e3:7.3f} ms poll {po*1e3:7.3f} ms",
+              file=sys.stderr)
 
-    elapsed = t1 - t0
     if dist is not None:
         import torch
         e = torch.tensor([elapsed], dtype=torch.float64)
@@ -391,6 +545,14 @@ def main():
         elapsed = float(e.item())
 
     stats = op.kernel_stats()
+
+    if args.dump_outputs and kept is not None:
+        t_last = 1_000_000 + ((W + K - 1) * B) // args.rows_per_ms
+        n_dump, sampled = dump_outputs(args.dump_outputs, kept, t_last,
+                                       args.seed, rank, world)
+        print(f"dumped {n_dump} output rows"
+              f"{' (seeded sample)' if sampled else ''} to "
+              f"{args.dump_outputs}", file=sys.stderr)
 
     if rank == 0:
         rows_timed = K * B * world  # whole-job rows through the timed region
@@ -499,7 +661,7 @@ def main():
             },
             "cpu_baseline": None,
         }
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
             if utf8:
                 out["cpu_baseline"]["sample"] += (
@@ -513,6 +675,13 @@ def main():
         join.close()
     if decoder is not None:
         decoder.close()
+    while scratch is not None and not scratch.empty():
+        sc = scratch.get()
+        sc["d_lens"].free()
+        if sc["d_offs"] is not None:
+            sc["d_offs"].free()
+    if varlen:
+        gen_pool.shutdown()
     for a in (d_ts, d_kid, d_vals, d_offs, d_data, d_trips):
         if a is not None:
             a.free()
