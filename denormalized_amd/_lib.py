@@ -17,10 +17,18 @@ DZ_OK = 0
 WINDOW_TUMBLING = 0
 WINDOW_SLIDING = 1
 AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM, AGG_AVG = 0, 1, 2, 3, 4
+AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP, AGG_STDDEV_POP = 5, 6, 7, 8
+VAR_AGGS = frozenset((AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP,
+                      AGG_STDDEV_POP))
 KEY_UTF8, KEY_INT64, KEY_DENSE_INT64 = 0, 1, 2
 CMP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "==": 4, "!=": 5}
 AGG_BY_NAME = {"count": AGG_COUNT, "min": AGG_MIN, "max": AGG_MAX,
-               "sum": AGG_SUM, "avg": AGG_AVG, "average": AGG_AVG}
+               "sum": AGG_SUM, "avg": AGG_AVG, "average": AGG_AVG,
+               # the reference's functions.py: var/stddev are the sample forms
+               "var_samp": AGG_VAR_SAMP, "var_sample": AGG_VAR_SAMP,
+               "var": AGG_VAR_SAMP, "var_pop": AGG_VAR_POP,
+               "stddev": AGG_STDDEV_SAMP, "stddev_samp": AGG_STDDEV_SAMP,
+               "stddev_pop": AGG_STDDEV_POP}
 
 
 class DzAggDesc(ctypes.Structure):
@@ -70,6 +78,9 @@ class DzOutBatch(ctypes.Structure):
         ("agg_valid", ctypes.POINTER(ctypes.c_uint8)),
         ("window_start_ms", ctypes.POINTER(ctypes.c_int64)),
         ("window_end_ms", ctypes.POINTER(ctypes.c_int64)),
+        # n_aggs per-aggregate byte masks; NULL entry = follows agg_valid;
+        # the pointer itself is NULL for ops without a variance aggregate
+        ("agg_valid_cols", ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))),
     ]
 
 
@@ -154,6 +165,13 @@ def lib():
                                        i64, i64, i64, i64, p, p, p]
         L.dz_debug_windows_for_range.restype = i64
         L.dz_debug_windows_for_range.argtypes = [i64, i64, i64, i64, p, p, i64]
+        try:
+            L.dz_debug_var_finalize.restype = ctypes.c_int32
+            L.dz_debug_var_finalize.argtypes = [
+                ctypes.c_int32, ctypes.c_uint64, ctypes.c_double,
+                ctypes.POINTER(ctypes.c_double)]
+        except AttributeError:  # older engine build (A/B hook)
+            pass
         L.dz_version.restype = ctypes.c_char_p
         _lib = L
     return _lib
@@ -183,8 +201,11 @@ class WindowOp:
         n = len(aggs)
         self._agg_arr = (DzAggDesc * n)()
         self.agg_names = []
+        self._var_aggs = []  # indices whose column has its own NULL mask
         for i, (name, _col) in enumerate(aggs):
             self._agg_arr[i].op = AGG_BY_NAME[name] if isinstance(name, str) else name
+            if self._agg_arr[i].op in VAR_AGGS:
+                self._var_aggs.append(i)
             self._agg_arr[i].input_col = value_col
             self.agg_names.append(name if isinstance(name, str) else str(name))
         d = DzWindowDesc(
@@ -314,6 +335,19 @@ class WindowOp:
             res["valid"] = v.copy() if copy else v
         else:
             res["valid"] = np.zeros(0, np.uint8)
+        for i in self._var_aggs:
+            # variance family: own NULL rule (e.g. var_samp of a one-row
+            # group), reported per aggregate
+            name = self.agg_names[i]
+            pm = ob.agg_valid_cols[i] if n and ob.agg_valid_cols else None
+            if pm:
+                v = np.ctypeslib.as_array(pm, (n,))
+                res[name + "_valid"] = v.copy() if copy else v
+            elif n:
+                raise RuntimeError(
+                    f"engine returned no validity mask for {name!r}")
+            else:
+                res[name + "_valid"] = np.zeros(0, np.uint8)
         res["window_start"] = mk(ob.window_start_ms, n, ctypes.c_int64)
         res["window_end"] = mk(ob.window_end_ms, n, ctypes.c_int64)
         return res

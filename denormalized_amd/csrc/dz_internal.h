@@ -91,13 +91,17 @@ constexpr int FOLD_GCAP = 256; /* groups per bucket per fold chunk */
 
 /* fused stable-split + fold: per-(window,key) bins staged in LDS fold
  * straight into register accumulators seeded from the window-slot slabs —
- * no reordered records in HBM */
+ * no reordered records in HBM. v_base != null selects the variance-carrying
+ * instantiation: the Welford (mean, m2) state lives in a side slab laid out
+ * [slot][{mean,m2}][kcap] f64 (vslab_cells = nslots * 2 * kcap), indexed by
+ * the same (slot, kloc, bucket) as the main slab and bounds-guarded through
+ * d_dbg; null keeps the kernels and the traffic of ops without it. */
 void launch_regroup_fold(hipStream_t stream, const uint4* d_grec,
                          const uint32_t* d_bucket_base,
                          const FoldChunk& fc, const int32_t* d_slot_of_widx,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
-                         uint32_t* d_dbg);
+                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells);
 
 void launch_regroup_l1(hipStream_t stream, const uint4* d_grec,
                        const uint32_t* d_bucket_base,
@@ -111,7 +115,8 @@ void launch_regroup_l2_fold(hipStream_t stream, const uint4* d_grec2,
                             const int32_t* d_slot_of_widx, uint64_t* s_cnt,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
-                            uint32_t* d_dbg);
+                            uint32_t* d_dbg, double* v_base,
+                            int64_t vslab_cells);
 
 struct EGatherSlots {
     int32_t s[16];
@@ -179,6 +184,11 @@ void launch_reset_slots(hipStream_t stream, const int32_t* d_slots, int ns,
 void launch_egather_slabs(hipStream_t stream, const uint64_t* s_base,
                           int64_t stride_u64, EGatherSlots slots, int gcount,
                           uint64_t* out);
+/* variance-declaring ops: 6 * kcap cells per close — the 5-field slab, then
+ * the slot's m2 column from the side slab */
+void launch_egather_slabs_var(hipStream_t stream, const uint64_t* s_base,
+                              const double* v_base, int64_t kcap,
+                              EGatherSlots slots, int gcount, uint64_t* out);
 void launch_arm_scalars(hipStream_t stream, uint64_t* scalars);
 
 void launch_fill_i64(hipStream_t stream, int64_t* d_p, int64_t n, int64_t v);

@@ -769,14 +769,34 @@ constexpr int GCAP = FOLD_GCAP; /* bins (groups) per bucket per chunk */
  * staging in place. */
 enum { RG_L1 = 1, RG_DIRECT_FOLD = 3, RG_L2_FOLD = 4 };
 
-template <int MODE>
+/* One Welford update of the variance family's (mean, m2) state; n is the
+ * group's valid-row count INCLUDING this row. Every operation is rounded on
+ * its own — the reference accumulator is plain Rust f64 arithmetic, and a
+ * fused m2 + d1*d2 differs from it in the last bit — so contraction is
+ * switched off for this body (hipcc contracts by default). */
+__device__ __forceinline__ void welford_step(double v, uint64_t n,
+                                             double& mean, double& m2) {
+#pragma clang fp contract(off)
+    const double d1 = v - mean;
+    const double nmean = d1 / (double)n + mean;
+    const double d2 = v - nmean;
+    m2 = m2 + d1 * d2;
+    mean = nmean;
+}
+
+/* VAR: the fold also carries the variance family's (mean, m2) accumulators,
+ * persisted in the side slab v_base ([slot][{mean,m2}][kcap] f64). VAR=false
+ * compiles to the kernels without them (v_base/vslab_cells unused). */
+template <int MODE, bool VAR = false>
 __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
         const uint32_t* bucket_base, FoldChunk fc,
         const uint32_t* b1offs, const uint32_t* b1lens, uint32_t* binoffs,
         uint32_t* binlens, uint4* orec,
         const int32_t* slot_of_widx, uint64_t* s_cnt, double* s_min,
         double* s_max, double* s_sum, uint64_t* s_first, int64_t slab_cells,
-        uint32_t* dbg) {
+        uint32_t* dbg, double* v_base, int64_t vslab_cells) {
+    static_assert(!VAR || MODE == RG_DIRECT_FOLD || MODE == RG_L2_FOLD,
+                  "only the fold modes carry variance state");
     constexpr bool FOLD = (MODE == RG_DIRECT_FOLD || MODE == RG_L2_FOLD);
     __shared__ uint32_t cnt[GCAP];    /* whole-segment bin counts (L1) */
     __shared__ uint32_t gcur[GCAP];   /* segment-region bin cursors (L1) */
@@ -833,6 +853,8 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     bool f_own = false, f_loaded = false;
     uint64_t f_cnt = 0, f_fst = ~0ULL;
     double f_mn = 0.0, f_mx = 0.0, f_sm = 0.0;
+    int64_t f_vidx = 0;               /* VAR: side-slab cell of `mean` */
+    double f_mean = 0.0, f_m2 = 0.0;  /* VAR: Welford state */
     if (FOLD) {
         const int g = threadIdx.x;
         int my_widx = 0, my_kloc = 0;
@@ -852,6 +874,17 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
             if (slot < 0 || f_sidx < 0 || f_sidx + 4 * fc.kcap >= slab_cells) {
                 dbg[1] = 1; /* bounds guard: disown, never corrupt */
                 f_own = false;
+            }
+            if (VAR) {
+                /* same (slot, kloc, bucket) indexing, 2 fields per slot;
+                 * m2 sits kcap cells after mean */
+                f_vidx = slot * (2 * fc.kcap) +
+                         (((int64_t)my_kloc << LOG_NB) | bkt);
+                if (slot < 0 || f_vidx < 0 ||
+                    f_vidx + fc.kcap >= vslab_cells) {
+                    dbg[1] = 1;
+                    f_own = false;
+                }
             }
         }
     }
@@ -977,6 +1010,13 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                         f_mn = s_min[f_sidx];
                         f_mx = s_max[f_sidx];
                         f_sm = s_sum[f_sidx];
+                        if (VAR) {
+                            /* gated on cnt > 0 like min/max/sum: a recycled
+                             * slot (cnt reset to 0) starts from (0, 0) in
+                             * registers whatever the side slab still holds */
+                            f_mean = v_base[f_vidx];
+                            f_m2 = v_base[f_vidx + fc.kcap];
+                        }
                     }
                 }
                 if (f_fst == ~0ULL)
@@ -991,6 +1031,7 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                         f_mx = (fresh || v > f_mx) ? v : f_mx;
                         f_sm += v;
                         f_cnt++;
+                        if (VAR) welford_step(v, f_cnt, f_mean, f_m2);
                     }
                 }
             }
@@ -1015,6 +1056,10 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
         s_min[f_sidx] = f_mn;
         s_max[f_sidx] = f_mx;
         s_sum[f_sidx] = f_sm;
+        if (VAR) {
+            v_base[f_vidx] = f_mean;
+            v_base[f_vidx + fc.kcap] = f_m2;
+        }
     }
 }
 
@@ -1023,11 +1068,19 @@ void launch_regroup_fold(hipStream_t s, const uint4* d_grec,
                          const FoldChunk& fc, const int32_t* d_slot_of_widx,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
-                         uint32_t* d_dbg) {
+                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells) {
+    if (v_base)
+        hipLaunchKernelGGL((k_regroup_t<RG_DIRECT_FOLD, true>), dim3(NB),
+                           dim3(BLOCK), 0, s, d_grec, d_bucket_base, fc,
+                           nullptr, nullptr, nullptr, nullptr, nullptr,
+                           d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first,
+                           slab_cells, d_dbg, v_base, vslab_cells);
+    else
     hipLaunchKernelGGL(k_regroup_t<RG_DIRECT_FOLD>, dim3(NB), dim3(BLOCK), 0, s,
                        d_grec, d_bucket_base, fc, nullptr, nullptr,
                        nullptr, nullptr, nullptr, d_slot_of_widx,
-                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg);
+                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg,
+                       nullptr, 0);
 }
 
 void launch_regroup_l1(hipStream_t s, const uint4* d_grec,
@@ -1036,7 +1089,7 @@ void launch_regroup_l1(hipStream_t s, const uint4* d_grec,
     hipLaunchKernelGGL(k_regroup_t<RG_L1>, dim3(NB), dim3(BLOCK), 0, s,
                        d_grec, d_bucket_base, fc, nullptr, nullptr, d_b1offs,
                        d_b1lens, d_grec2, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0, nullptr);
+                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0);
 }
 
 void launch_regroup_l2_fold(hipStream_t s, const uint4* d_grec2,
@@ -1046,11 +1099,20 @@ void launch_regroup_l2_fold(hipStream_t s, const uint4* d_grec2,
                             const int32_t* d_slot_of_widx, uint64_t* s_cnt,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
-                            uint32_t* d_dbg) {
+                            uint32_t* d_dbg, double* v_base,
+                            int64_t vslab_cells) {
+    if (v_base)
+        hipLaunchKernelGGL((k_regroup_t<RG_L2_FOLD, true>), dim3(NB, nb1),
+                           dim3(BLOCK), 0, s, d_grec2, d_bucket_base, fc,
+                           d_b1offs, d_b1lens, nullptr, nullptr, nullptr,
+                           d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first,
+                           slab_cells, d_dbg, v_base, vslab_cells);
+    else
     hipLaunchKernelGGL(k_regroup_t<RG_L2_FOLD>, dim3(NB, nb1), dim3(BLOCK), 0, s,
                        d_grec2, d_bucket_base, fc, d_b1offs, d_b1lens,
                        nullptr, nullptr, nullptr, d_slot_of_widx,
-                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg);
+                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg,
+                       nullptr, 0);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1469,6 +1531,33 @@ void dz::launch_egather_slabs(hipStream_t s, const uint64_t* s_base,
     dim3 grid(bx, gcount);
     hipLaunchKernelGGL(k_egather_slabs, grid, dim3(dz::BLOCK), 0, s, s_base,
                        stride_u64, slots, out);
+}
+
+/* variance-declaring ops: each packed close is the 5-field slab followed by
+ * the slot's m2 column from the side slab (6 * kcap cells per close) */
+__global__ void k_egather_slabs_var(const uint64_t* __restrict__ s_base,
+                                    const uint64_t* __restrict__ v_base,
+                                    int64_t kcap, dz::EGatherSlots slots,
+                                    uint64_t* __restrict__ out) {
+    const int g = blockIdx.y;
+    const int64_t slot = slots.s[g];
+    const uint64_t* src = s_base + slot * (5 * kcap);
+    const uint64_t* m2 = v_base + slot * (2 * kcap) + kcap;
+    uint64_t* dst = out + (int64_t)g * (6 * kcap);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < 6 * kcap; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = i < 5 * kcap ? src[i] : m2[i - 5 * kcap];
+}
+
+void dz::launch_egather_slabs_var(hipStream_t s, const uint64_t* s_base,
+                                  const double* v_base, int64_t kcap,
+                                  dz::EGatherSlots slots, int gcount,
+                                  uint64_t* out) {
+    int bx = (int)std::min<int64_t>((6 * kcap + dz::BLOCK - 1) / dz::BLOCK,
+                                    512);
+    dim3 grid(bx, gcount);
+    hipLaunchKernelGGL(k_egather_slabs_var, grid, dim3(dz::BLOCK), 0, s,
+                       s_base, (const uint64_t*)v_base, kcap, slots, out);
 }
 
 /* arm the per-push scalar block (min=+inf pattern, max/kid=0) in ONE tiny

@@ -10,6 +10,7 @@
 #include "denormalized_amd.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <deque>
@@ -61,6 +62,29 @@ extern "C" int64_t dz_debug_windows_for_range(int64_t min_ts, int64_t max_ts,
         }
     }
     return n;
+}
+
+static inline bool is_var_op(int32_t o) {
+    return o >= DZ_AGG_VAR_SAMP && o <= DZ_AGG_STDDEV_POP;
+}
+
+/* Finalise rule of the variance family (DataFusion VarianceAccumulator /
+ * StddevAccumulator evaluate()): the ONE copy — emission and the filter call
+ * it too. Division and sqrt are correctly rounded host operations. */
+extern "C" int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count,
+                                         double m2, double* out) {
+    if (!is_var_op(agg_op)) return -1;
+    const bool pop = agg_op == DZ_AGG_VAR_POP || agg_op == DZ_AGG_STDDEV_POP;
+    const uint64_t div = pop ? count : count - 1;
+    if (count == 0 || div == 0) {
+        if (out) *out = 0.0;
+        return 0;
+    }
+    double v = m2 / (double)div;
+    if (agg_op == DZ_AGG_STDDEV_SAMP || agg_op == DZ_AGG_STDDEV_POP)
+        v = std::sqrt(v);
+    if (out) *out = v;
+    return 1;
 }
 
 extern "C" const char* dz_version(void) { return "denormalized-amd 0.1 (gfx950)"; }
@@ -146,9 +170,13 @@ struct OutBuf {
     std::vector<std::vector<int64_t>> agg_i64; /* per agg col (COUNT) */
     std::vector<std::vector<double>> agg_f64;  /* per agg col (others) */
     std::vector<uint8_t> agg_valid;
+    /* per-aggregate masks: filled for variance-family columns only (their
+     * NULL rule differs from agg_valid); empty = follows agg_valid */
+    std::vector<std::vector<uint8_t>> agg_valid_a;
     std::vector<int64_t> wstart, wend;
     /* view plumbing */
     std::vector<const void*> agg_ptrs;
+    std::vector<const uint8_t*> valid_ptrs;
     dz_out_batch view;
 };
 
@@ -197,6 +225,15 @@ struct dz_window_op {
     double* s_min = nullptr;
     double* s_max = nullptr;
     double* s_sum = nullptr;
+    /* variance family (has_var): Welford (mean, m2) side slab,
+     * [slot][{mean,m2}][kcap] f64 — allocated only when an aggregate of the
+     * family is declared; the main slab keeps its 5*kcap stride. Slot reuse
+     * needs no reset here: the fold seeds mean/m2 from it only while the
+     * main slab's cnt > 0, and k_reset_slots zeroes cnt. Such ops emit
+     * through the host-built path at every key count (m2 travels as a 6th
+     * column of the packed slab; finalisation is host-side). */
+    bool has_var = false;
+    double* v_base = nullptr;
     struct FreeSlot {
         int32_t slot;
         hipEvent_t ev;     /* copy-done gate or null */
@@ -349,6 +386,11 @@ struct dz_window_op {
                                           * a kernel store does not */
     std::vector<int> e_gfree;            /* guarded by e_mtx */
     int64_t e_gbuf_kcap = 0;
+    /* variance-declaring ops use the group buffers at EVERY key count:
+     * closes per buffer (1..16) and the buffer's size in 8-byte cells, so
+     * the enqueue can prove a group fits before it launches the gather */
+    int32_t e_gbuf_closes = 0;
+    int64_t e_gbuf_cells = 0;
     /* zero-copy OutBufs hold pinned slabs across a pool regrow (keyspace
      * growth): old allocations go to a graveyard until destroy, and a
      * generation counter stops a stale hold from re-entering the new pool */
@@ -553,10 +595,28 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
                                    op->s_base + s * stride_old + (size_t)f * op->kcap,
                                    span * 8, hipMemcpyDeviceToDevice, op->stream));
     }
+    double* n_vbase = nullptr;
+    if (op->has_var) {
+        size_t vstride_new = (size_t)kcap_new * 2, vstride_old = (size_t)op->kcap * 2;
+        CHK(op, hipMalloc(&n_vbase, vstride_new * nslots_new * 8));
+        CHK(op, hipMemsetAsync(n_vbase, 0, vstride_new * nslots_new * 8, op->stream));
+        for (auto& kv : op->open) {
+            int32_t s = kv.second.slot;
+            int64_t span = std::min(op->kcap, kcap_new);
+            for (int f = 0; f < 2; f++)
+                CHK(op, hipMemcpyAsync(n_vbase + s * vstride_new + (size_t)f * kcap_new,
+                                       op->v_base + s * vstride_old + (size_t)f * op->kcap,
+                                       span * 8, hipMemcpyDeviceToDevice, op->stream));
+        }
+    }
     CHK(op, hipStreamSynchronize(op->stream));
     for (int s = 0; s < dz_window_op::E_CSTREAMS; s++) /* emission reads s_base */
         if (op->c_streams[s])
             CHK(op, hipStreamSynchronize(op->c_streams[s]));
+    if (op->has_var) {
+        hipFree(op->v_base);
+        op->v_base = n_vbase;
+    }
     hipFree(op->s_base);
     op->s_base = n_base;
     op->s_cnt = n_cnt; op->s_first = n_first; op->s_min = n_min;
@@ -582,6 +642,16 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
         return nullptr;
     }
     if (desc->n_aggs <= 0 || !desc->aggs) { g_err = "need at least one aggregate"; return nullptr; }
+    bool any_var = false;
+    for (int32_t a = 0; a < desc->n_aggs; a++) {
+        const int32_t o = (int32_t)desc->aggs[a].op;
+        if (o < DZ_AGG_COUNT || o > DZ_AGG_STDDEV_POP) {
+            g_err = "aggregate " + std::to_string(a) + ": unknown op code " +
+                    std::to_string(o) + " (valid: 0..8, see dz_agg_op)";
+            return nullptr;
+        }
+        any_var = any_var || is_var_op(o);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= desc->device) {
         g_err = "no HIP device available (this operator has no CPU fallback)";
@@ -596,6 +666,7 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
     op->no_group = desc->group_col < 0;
     op->key_kind = op->no_group ? DZ_KEY_DENSE_INT64 : desc->key_kind;
     op->aggs.assign(desc->aggs, desc->aggs + desc->n_aggs);
+    op->has_var = any_var;
     op->device = desc->device;
     op->max_open = desc->max_open_windows > 0 ? desc->max_open_windows : 4096;
     bool cs_ok = true;
@@ -691,6 +762,7 @@ extern "C" void dz_window_op_destroy(dz_window_op* op) {
         hipFree(op->d_roffs[s]);
     }
     hipFree(op->s_base);
+    hipFree(op->v_base);
     hipFree(op->d_ghist[0]); hipFree(op->d_ghist[1]);
     hipFree(op->d_gofs[0]); hipFree(op->d_gofs[1]);
     hipFree(op->d_total[0]); hipFree(op->d_total[1]);
@@ -742,12 +814,17 @@ extern "C" const char* dz_last_error(dz_window_op* op) {
 
 
 static bool filter_pass(dz_window_op* op, int64_t row_cnt,
-                        double vmin, double vmax, double vsum, bool valid) {
+                        double vmin, double vmax, double vsum, double vm2,
+                        bool valid) {
     if (!op->has_filter) return true;
     double v;
     dz_agg_op o = op->aggs[op->f_idx].op;
     if (o == DZ_AGG_COUNT) {
         v = (double)row_cnt;
+    } else if (is_var_op(o)) {
+        /* the comparison runs on the finalised value; NULL never passes */
+        if (dz_debug_var_finalize(o, (uint64_t)row_cnt, vm2, &v) != 1)
+            return false;
     } else {
         if (!valid) return false; /* NULL never passes a comparison filter */
         switch (o) {
@@ -770,7 +847,8 @@ static bool filter_pass(dz_window_op* op, int64_t row_cnt,
 }
 
 /* Build one emitted batch from a pinned copy of a slot slab
- * ([cnt][first][min][max][sum], each `kcap` 8-byte entries). Runs on the
+ * ([cnt][first][min][max][sum], each `kcap` 8-byte entries; variance-
+ * declaring ops append [m2] from the side slab). Runs on the
  * emission worker thread: touches only immutable config, the deque-backed
  * dictionaries (indices < the job's n_keys snapshot) and the slab. */
 static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
@@ -781,6 +859,8 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const double* f_min = (const double*)(slab + 2 * kcap);
     const double* f_max = (const double*)(slab + 3 * kcap);
     const double* f_sum = (const double*)(slab + 4 * kcap);
+    const double* f_m2 =
+        op->has_var ? (const double*)(slab + 5 * kcap) : nullptr;
 
     /* groups in first-seen (insertion) order: GroupValues emits insertion
      * order; sort touched keys by first-row sequence (first values are
@@ -813,7 +893,8 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     for (auto& p : touched) {
         int32_t k = p.second;
         int64_t cnt = (int64_t)f_cnt[k];
-        if (filter_pass(op, cnt, f_min[k], f_max[k], f_sum[k], cnt > 0))
+        if (filter_pass(op, cnt, f_min[k], f_max[k], f_sum[k],
+                        f_m2 ? f_m2[k] : 0.0, cnt > 0))
             rows.push_back(k);
     }
     size_t n = rows.size(), na = op->aggs.size();
@@ -821,6 +902,7 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     OutBuf& ob = *out;
     ob.agg_i64.resize(na);
     ob.agg_f64.resize(na);
+    if (op->has_var) ob.agg_valid_a.resize(na);
     if (op->key_kind == DZ_KEY_UTF8) {
         ob.key_offsets.resize(n + 1);
         ob.key_offsets[0] = 0;
@@ -877,6 +959,20 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                     uint64_t c = f_cnt[rows[i]];
                     col[i] = c ? f_sum[rows[i]] / (double)c : 0.0;
                 }
+                break;
+            }
+            case DZ_AGG_VAR_SAMP:
+            case DZ_AGG_VAR_POP:
+            case DZ_AGG_STDDEV_SAMP:
+            case DZ_AGG_STDDEV_POP: {
+                auto& col = ob.agg_f64[a];
+                auto& msk = ob.agg_valid_a[a];
+                col.resize(n);
+                msk.resize(n);
+                for (size_t i = 0; i < n; i++)
+                    msk[i] = (uint8_t)dz_debug_var_finalize(
+                        op->aggs[a].op, f_cnt[rows[i]], f_m2[rows[i]],
+                        &col[i]);
                 break;
             }
         }
@@ -983,6 +1079,7 @@ static OutBuf take_outbuf(dz_window_op* op) {
     for (auto& c : ob.agg_i64) c.clear();
     for (auto& c : ob.agg_f64) c.clear();
     ob.agg_valid.clear();
+    for (auto& c : ob.agg_valid_a) c.clear();
     ob.wstart.clear();
     ob.wend.clear();
     return ob;
@@ -1141,7 +1238,8 @@ static void emit_worker_main(dz_window_op* op) {
             /* gbuf jobs: job.ev = gather done, and the gather wrote this
              * close's slab directly into the pinned group buffer */
             const uint64_t* slab = job.gbuf >= 0
-                ? op->e_gbufs[job.gbuf] + (size_t)job.goff * job.kcap * 5
+                ? op->e_gbufs[job.gbuf] +
+                      (size_t)job.goff * job.kcap * (op->has_var ? 6 : 5)
                 : op->e_slabs[job.slab];
             build_emission_host(op, job.wstart, job.wend, job.n_keys, job.kcap,
                                 slab, &ob);
@@ -1240,9 +1338,18 @@ static dz_status ensure_emission(dz_window_op* op) {
                 hipHostFree(op->e_gbufs[i]);
                 op->e_gbufs[i] = nullptr;
             }
-        bool have_gbufs = kc <= 65536;
+        /* variance-declaring ops emit host-built at EVERY key count, so
+         * their group buffers exist at every kcap: as many whole 6-column
+         * closes as fit a 64 MiB budget (at least one, at most EGROUP) */
+        bool have_gbufs = kc <= 65536 || op->has_var;
+        op->e_gbuf_closes = dz_window_op::E_POOL / 2;
+        if (op->has_var)
+            op->e_gbuf_closes = (int32_t)std::min<int64_t>(
+                dz_window_op::E_POOL / 2,
+                std::max<int64_t>(1, ((int64_t)64 << 20) / (kc * 6 * 8)));
+        op->e_gbuf_cells = (int64_t)op->e_gbuf_closes * kc * (op->has_var ? 6 : 5);
         if (have_gbufs) {
-            size_t gbytes = (size_t)(dz_window_op::E_POOL / 2) * kc * 5 * 8;
+            size_t gbytes = (size_t)op->e_gbuf_cells * 8;
             for (int i = 0; i < dz_window_op::E_GBUFS; i++) {
                 CHK(op, hipHostMalloc((void**)&op->e_gbufs[i], gbytes,
                                       hipHostMallocMapped));
@@ -1461,7 +1568,9 @@ static dz_status trigger_windows(dz_window_op* op) {
      * slabs whose release depends on this group's phase 2 (deadlock). */
     struct Pending { int slab; hipEvent_t ev; };
     constexpr size_t EGROUP = dz_window_op::E_POOL / 2;
-    const bool dev_path_g = op->n_keys > 65536;
+    /* variance-declaring ops take the host-built path at every key count
+     * (the device chains carry no m2 column) */
+    const bool dev_path_g = op->n_keys > 65536 && !op->has_var;
     /* group-batched device path: a whole trigger group of SMALL closes in
      * ONE chain (~25 host enqueues total instead of per close — the
      * push-thread enqueue serialization was the cfg3 sliding wall). Large
@@ -1479,6 +1588,8 @@ static dz_status trigger_windows(dz_window_op* op) {
     size_t g0 = 0;
     while (g0 < closed.size()) {
     size_t gstep = EGROUP;
+    if (op->has_var)
+        gstep = std::min<size_t>(gstep, (size_t)std::max(1, op->e_gbuf_closes));
     if (grouped_ok)
         gstep = std::min<size_t>(gstep, std::max<size_t>(1,
             (size_t)(dz_window_op::E_GELEMS / op->kcap)));
@@ -1613,6 +1724,18 @@ static dz_status trigger_windows(dz_window_op* op) {
              * fully asynchronous for the push thread (hipMemcpyAsync D2H
              * was measured performing the transfer at ENQUEUE time) */
             HostTimer htg(op, "h_trig_gather");
+            if (op->has_var) {
+                if ((int64_t)gcount * 6 * op->kcap > op->e_gbuf_cells) {
+                    op->err = "internal: emission group of " +
+                              std::to_string(gcount) + " closes x " +
+                              std::to_string(op->kcap) +
+                              " keys overflows the pinned group buffer";
+                    return DZ_ERR;
+                }
+                dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
+                                             op->v_base, op->kcap, gs, gcount,
+                                             op->e_gbufs_dev[gbuf]);
+            } else
             dz::launch_egather_slabs(op->copy_stream, op->s_base, stride, gs,
                                      gcount, op->e_gbufs_dev[gbuf]);
             CHK(op, hipEventRecord(fr, op->copy_stream));
@@ -1642,6 +1765,13 @@ static dz_status trigger_windows(dz_window_op* op) {
         op->e_cv.notify_all();
         g0 = g1;
         continue;
+    }
+    if (op->has_var) {
+        /* unreachable while ensure_emission holds: the per-close staging
+         * below carries no m2 column — refuse rather than emit without it */
+        op->err = "internal: variance aggregates need the pinned group "
+                  "buffers (allocation missing)";
+        return DZ_ERR;
     }
     std::vector<Pending> pend;
     pend.reserve(g1 - g0);
@@ -2151,7 +2281,8 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                                            op->s_min, op->s_max, op->s_sum,
                                            op->s_first,
                                            (int64_t)op->nslots * 5 * op->kcap,
-                                           op->d_dbg);
+                                           op->d_dbg, op->v_base,
+                                           (int64_t)op->nslots * 2 * op->kcap);
             });
         } else {
             for (int64_t k_lo = 0; k_lo < klocs; k_lo += dz::FOLD_GCAP) {
@@ -2173,7 +2304,9 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                             op->stream, op->d_grec, op->d_base[b], fc,
                             op->d_slotmap + W0, op->s_cnt, op->s_min,
                             op->s_max, op->s_sum, op->s_first,
-                            (int64_t)op->nslots * 5 * op->kcap, op->d_dbg);
+                            (int64_t)op->nslots * 5 * op->kcap, op->d_dbg,
+                            op->v_base,
+                            (int64_t)op->nslots * 2 * op->kcap);
                     });
                 }
             }
@@ -2642,6 +2775,15 @@ extern "C" dz_status dz_window_op_poll(dz_window_op* op, const dz_out_batch** ou
         ob.view.agg_valid = ob.agg_valid.data();
     }
     ob.view.agg_cols = ob.agg_ptrs.data();
+    ob.view.agg_valid_cols = nullptr;
+    if (op->has_var) {
+        ob.valid_ptrs.clear();
+        for (size_t a = 0; a < op->aggs.size(); a++)
+            ob.valid_ptrs.push_back(
+                is_var_op(op->aggs[a].op) && a < ob.agg_valid_a.size()
+                    ? ob.agg_valid_a[a].data() : nullptr);
+        ob.view.agg_valid_cols = ob.valid_ptrs.data();
+    }
     ob.view.window_start_ms = ob.wstart.data();
     ob.view.window_end_ms = ob.wend.data();
     *out = &ob.view;

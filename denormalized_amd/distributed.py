@@ -10,11 +10,23 @@ rank-major, matching the reference's partition-merge structure rather than
 single-stream row order — see DESIGN.md)."""
 import numpy as np
 
+from ._lib import AGG_BY_NAME, VAR_AGGS
+
+_VAR_NAMES = frozenset(n for n, code in AGG_BY_NAME.items() if code in VAR_AGGS)
+
 
 def merge_global_partials(per_rank_batches):
     """per_rank_batches: list (rank order) of lists of emitted batches from a
     no-group WindowOp (each batch: one window, one row, with 'count'/'min'/
     'max'/'sum' or 'avg' columns). Returns merged rows keyed by window."""
+    for batches in per_rank_batches:
+        for b in batches:
+            bad = sorted(k for k in b if k in _VAR_NAMES)
+            if bad:
+                raise ValueError(
+                    f"merge_global_partials cannot merge {bad}: combining "
+                    "Welford (count, mean, m2) partials needs a different "
+                    "formula than count/min/max/sum and is not supported")
     acc = {}  # (wstart, wend) -> [count, min, max, sum, any_valid]
     order = []
     for batches in per_rank_batches:

@@ -36,13 +36,24 @@ typedef enum dz_window_type {
 } dz_window_type;
 
 /* The aggregate set of the hot path (simple_aggregation.rs:46-52:
- * count/min/max/avg; sum is the avg partial and is also exposed). */
+ * count/min/max/avg; sum is the avg partial and is also exposed), plus the
+ * variance family of the reference's Python example
+ * (py-denormalized/python/examples/stream_aggregate.py:52-53). */
 typedef enum dz_agg_op {
     DZ_AGG_COUNT = 0,
     DZ_AGG_MIN   = 1,
     DZ_AGG_MAX   = 2,
     DZ_AGG_SUM   = 3,
     DZ_AGG_AVG   = 4,
+    /* Welford variance family (the reference's stddev/stddev_pop/var_samp/
+     * var_pop, py-denormalized/python/denormalized/datafusion/functions.py):
+     * per-group state (count, mean, m2), updated per valid row in row order.
+     * NULL when count == 0 (pop) or count <= 1 (samp) — reported through
+     * dz_out_batch.agg_valid_cols. */
+    DZ_AGG_VAR_SAMP    = 5,
+    DZ_AGG_VAR_POP     = 6,
+    DZ_AGG_STDDEV_SAMP = 7,
+    DZ_AGG_STDDEV_POP  = 8,
 } dz_agg_op;
 
 typedef enum dz_key_kind {
@@ -118,6 +129,13 @@ typedef struct dz_out_batch {
                                     * (all-null groups); count is never null */
     const int64_t* window_start_ms;
     const int64_t* window_end_ms;
+    /* per-aggregate byte masks, n_aggs entries (appended field; everything
+     * above keeps its offset and meaning). Entry a is the mask of aggregate
+     * a; a NULL entry means that aggregate follows agg_valid. The variance
+     * family has its own NULL rule (var_samp of a one-row group is NULL
+     * while its min is valid), so its entries are non-NULL. The pointer
+     * itself may be NULL for ops that declare no variance aggregate. */
+    const uint8_t* const* agg_valid_cols;
 } dz_out_batch;
 
 /* ------------------------------------------------------------------ */
@@ -129,7 +147,8 @@ typedef struct dz_window_op dz_window_op;
 /* ExecutionPlan construction + execute(partition) →
  * GroupedWindowAggStream::new (streaming_window.rs:421-482,
  * grouped_window_agg_stream.rs:111-214). One handle = one partition's
- * stream; single-consumer. Returns NULL on error (see dz_last_error(NULL)). */
+ * stream; single-consumer. Returns NULL on error (see dz_last_error(NULL));
+ * an aggregate op code outside dz_agg_op is such an error. */
 dz_window_op* dz_window_op_create(const dz_window_desc* desc);
 
 /* One input batch == one poll of the input stream
@@ -213,7 +232,8 @@ int64_t dz_window_op_open_windows(dz_window_op* op);
  * (datastream.rs:94-105) evaluates over the window's output; pushing it
  * into the operator's emission keeps the boundary drop-in (output batches
  * are already filtered). cmp: 0 '<', 1 '<=', 2 '>', 3 '>=', 4 '==', 5 '!='.
- * agg_idx indexes dz_window_desc.aggs. NULL aggregate values never pass. */
+ * agg_idx indexes dz_window_desc.aggs. NULL aggregate values never pass
+ * (for the variance family: the finalised value, under its own NULL rule). */
 dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
                                   int32_t cmp, double literal);
 
@@ -353,6 +373,14 @@ dz_status dz_window_op_kernel_stats(dz_window_op* op, dz_kernel_stat* out,
 int64_t dz_debug_windows_for_range(int64_t min_ts, int64_t max_ts,
                                    int64_t len_ms, int64_t slide_ms,
                                    int64_t* starts, int64_t* ends, int64_t cap);
+
+/* Finalise rule of the variance family, shared with emission (which calls
+ * this same function): var_pop = m2/count (NULL when count == 0), var_samp =
+ * m2/(count-1) (NULL when count <= 1), stddev_* = sqrt of those. Writes the
+ * value to *out and returns 1 when valid, 0 when NULL (*out = 0.0), -1 when
+ * agg_op is not one of the four variance codes. */
+int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count, double m2,
+                              double* out);
 
 const char* dz_version(void);
 
