@@ -2,7 +2,9 @@
  * (window_op.cpp) and the CDNA4 kernels (kernels.hip). Not part of the C ABI.
  */
 #pragma once
+#include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 namespace dz {
@@ -130,6 +132,74 @@ struct EmitFilter {
     int32_t cmp;     /* 0 < 1 <= 2 > 3 >= 4 == 5 != */
     double lit;
 };
+
+/* The pushed-down filter rule, shared by the device chains (k_efilter,
+ * k_egf) and the host build: the count compares as a double; every other
+ * field is NULL for an empty group, and NULL never passes a comparison.
+ * A comparator code outside 0..5 compares as != here (the device chains'
+ * long-standing default arm). The host build has always let such a code
+ * pass every non-NULL group instead; filter_pass (window_op.cpp) keeps that
+ * rule in front of this call — the two are deliberately NOT unified. */
+__host__ __device__ inline bool emit_filter_pass(const EmitFilter& ef,
+                                                 uint64_t cnt, double mn,
+                                                 double mx, double sum) {
+    double v;
+    if (ef.field == 0) {
+        v = (double)cnt;
+    } else {
+        if (cnt == 0) return false;
+        switch (ef.field) {
+            case 1: v = mn; break;
+            case 2: v = mx; break;
+            case 3: v = sum; break;
+            default: v = sum / (double)cnt; break;
+        }
+    }
+    switch (ef.cmp) {
+        case 0: return v < ef.lit;
+        case 1: return v <= ef.lit;
+        case 2: return v > ef.lit;
+        case 3: return v >= ef.lit;
+        case 4: return v == ef.lit;
+        default: return v != ef.lit;
+    }
+}
+
+/* The packed emission row: the device chains' final-order output, pulled D2H
+ * as one span and read by the host builders and by poll()'s zero-copy views.
+ * Column-major, `stride` rows per column section:
+ *   [key i64][cnt u64][min f64][max f64][sum f64][avg f64][kid u32][flags u8]
+ * packed_cols() is the ONLY place that spells the section offsets. */
+constexpr int PACKED_ROW_BYTES = 53;
+
+template <typename B> /* B = char (writable) or const char (read-only) */
+struct PackedColsT {
+    template <typename T>
+    using P = typename std::conditional<std::is_const<B>::value, const T,
+                                        T>::type*;
+    P<int64_t> key;
+    P<uint64_t> cnt;
+    P<double> min, max, sum, avg;
+    P<uint32_t> kid;
+    P<uint8_t> flags; /* validity, 0/1 */
+};
+using PackedCols = PackedColsT<const char>;
+
+/* column pointers of a packed span of `stride` rows, advanced to row `off` */
+template <typename B>
+__host__ __device__ inline PackedColsT<B> packed_cols(B* base, size_t stride,
+                                                      size_t off = 0) {
+    PackedColsT<B> c;
+    c.key = (decltype(c.key))base + off;
+    c.cnt = (decltype(c.cnt))(base + stride * 8) + off;
+    c.min = (decltype(c.min))(base + stride * 16) + off;
+    c.max = (decltype(c.max))(base + stride * 24) + off;
+    c.sum = (decltype(c.sum))(base + stride * 32) + off;
+    c.avg = (decltype(c.avg))(base + stride * 40) + off;
+    c.kid = (decltype(c.kid))(base + stride * 48) + off;
+    c.flags = (decltype(c.flags))(base + stride * 52) + off;
+    return c;
+}
 
 /* device-side emission at window close, two stages on the copy stream:
  * slabread = compact touched groups + gather aggregate columns + filter

@@ -1127,36 +1127,59 @@ constexpr int RBINS = 1 << RDIG;  /* 2048 */
 constexpr int RCHUNK = 4096;      /* elements per radix block */
 constexpr int RPASSES = 6;        /* 6*11 = 66 >= 64 bits */
 
+/* Block compaction: every thread of a BLOCK-sized block calls this once per
+ * round with its `pass` flag; passers get a distinct output position from
+ * one `counter` bump per block (a returning per-thread atomic on one word
+ * serialises). Rank = wave ballot + per-wave sums in LDS; block-local order
+ * is irrelevant pre-sort. `wsum`/`base` are the caller's shared cells; the
+ * caller keeps a __syncthreads() between rounds. *tot_out = block passers. */
+__device__ __forceinline__ uint32_t block_compact_pos(
+        bool pass, uint32_t* counter, uint32_t* wsum /*[WAVES_PER_BLOCK]*/,
+        uint32_t* base, uint32_t* tot_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t m = __ballot(pass);
+    const uint64_t below = (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
+    const uint32_t wrank = (uint32_t)__popcll(m & below) - (pass ? 1 : 0);
+    if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t wbase = 0, tot = 0;
+    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
+        if (w < wave) wbase += wsum[w];
+        tot += wsum[w];
+    }
+    if (threadIdx.x == 0) *base = tot ? atomicAdd(counter, tot) : 0u;
+    __syncthreads();
+    *tot_out = tot;
+    return *base + wbase + wrank;
+}
+
+/* emit_filter_pass straight off a slot slab: the rule reads ONE of the three
+ * value columns (field is launch-uniform), so only that one is loaded — the
+ * closing slabs are the traffic of these kernels, and most groups fail the
+ * filter before any other column is needed. */
+__device__ __forceinline__ bool slab_filter_pass(const EmitFilter& ef,
+        uint64_t cnt, const double* s_min, const double* s_max,
+        const double* s_sum, int64_t k) {
+    const double* col = ef.field == 1 ? s_min : ef.field == 2 ? s_max : s_sum;
+    const double x = (ef.field != 0 && cnt > 0) ? col[k] : 0.0;
+    return emit_filter_pass(ef, cnt, x, x, x);
+}
+
 __global__ __launch_bounds__(BLOCK) void k_ecompact(const uint64_t* s_first,
         uint64_t fbase, int64_t K, uint64_t* ekeys, uint32_t* ekid,
         uint32_t* eiota, uint32_t* counter) {
-    /* one counter atomic per BLOCK (a returning per-thread atomic on one
-     * word serialises); block-local order is irrelevant pre-sort */
     __shared__ uint32_t base;
+    __shared__ uint32_t wsum[WAVES_PER_BLOCK];
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t k0 = (int64_t)blockIdx.x * blockDim.x; k0 < K;
          k0 += stride) {
         int64_t k = k0 + threadIdx.x;
         uint64_t f = (k < K) ? s_first[k] : ~0ULL;
         const bool hit = f != ~0ULL;
-        /* block count + intra-block rank via wave ballots + LDS */
-        __shared__ uint32_t wsum[WAVES_PER_BLOCK];
-        const int lane = threadIdx.x & 63;
-        const int wave = threadIdx.x >> 6;
-        const uint64_t m = __ballot(hit);
-        const uint64_t below = (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
-        const uint32_t wrank = (uint32_t)__popcll(m & below) - (hit ? 1 : 0);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t wbase = 0, tot = 0;
-        for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-            if (w < wave) wbase += wsum[w];
-            tot += wsum[w];
-        }
-        if (threadIdx.x == 0) base = tot ? atomicAdd(counter, tot) : 0u;
-        __syncthreads();
+        uint32_t tot;
+        const uint32_t p = block_compact_pos(hit, counter, wsum, &base, &tot);
         if (hit) {
-            uint32_t p = base + wbase + wrank;
             ekeys[p] = f - fbase; /* window-rebased: small keys, 4 passes */
             ekid[p] = (uint32_t)k;
             eiota[p] = p;
@@ -1331,55 +1354,16 @@ __global__ __launch_bounds__(BLOCK) void k_efilter(const uint64_t* ekeys,
     __shared__ uint32_t wsum[WAVES_PER_BLOCK];
     const uint32_t nt = *counter;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < nt; i0 += stride) {
         int64_t i = i0 + threadIdx.x;
         const bool act = i < nt;
         const uint32_t kid = act ? ekid[i] : 0;
         bool pass = act;
-        if (act && ef.on) {
-            const uint64_t c = s_cnt[kid];
-            const bool valid = c > 0;
-            double v = 0.0;
-            bool fv = true;
-            switch (ef.field) {
-                case 0: v = (double)c; break;
-                case 1: v = valid ? s_min[kid] : 0.0; fv = valid; break;
-                case 2: v = valid ? s_max[kid] : 0.0; fv = valid; break;
-                case 3: v = valid ? s_sum[kid] : 0.0; fv = valid; break;
-                default:
-                    v = valid ? s_sum[kid] / (double)c : 0.0;
-                    fv = valid;
-                    break;
-            }
-            if (!fv) {
-                pass = false; /* NULL never passes a comparison filter */
-            } else {
-                switch (ef.cmp) {
-                    case 0: pass = v < ef.lit; break;
-                    case 1: pass = v <= ef.lit; break;
-                    case 2: pass = v > ef.lit; break;
-                    case 3: pass = v >= ef.lit; break;
-                    case 4: pass = v == ef.lit; break;
-                    default: pass = v != ef.lit; break;
-                }
-            }
-        }
-        const uint64_t m = __ballot(pass);
-        const uint64_t below = (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
-        const uint32_t wrank = (uint32_t)__popcll(m & below) - (pass ? 1 : 0);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t wbase = 0, tot = 0;
-        for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-            if (w < wave) wbase += wsum[w];
-            tot += wsum[w];
-        }
-        if (threadIdx.x == 0) base = tot ? atomicAdd(counter2, tot) : 0u;
-        __syncthreads();
+        if (act && ef.on)
+            pass = slab_filter_pass(ef, s_cnt[kid], s_min, s_max, s_sum, kid);
+        uint32_t tot;
+        const uint32_t p = block_compact_pos(pass, counter2, wsum, &base, &tot);
         if (pass) {
-            uint32_t p = base + wbase + wrank;
             fkeys[p] = ekeys[i];
             fkid[p] = kid;
             fiota[p] = p;
@@ -1585,9 +1569,9 @@ void dz::launch_zero_counters(hipStream_t st, uint32_t* p) {
 /* apply the sorted permutation to every output column ON DEVICE, packing
  * the final-order columns into one contiguous block: the worker then pulls
  * ONE span and builds with sequential copies (the host-side gather through
- * sidx over ~1M-row closes was the cfg3 build bottleneck). Layout (by nt,
- * device-computed from counter2): [key i64][cnt u64][min][max][sum][avg]
- * [kid u32][flags u8] = 53 B/row. */
+ * sidx over ~1M-row closes was the cfg3 build bottleneck). The layout is
+ * dz::packed_cols (dz_internal.h) with stride nt, device-read from counter2.
+ * Serves the per-close chain and the group-batched chain alike. */
 __global__ void k_epermute(const uint32_t* __restrict__ counter2,
                            const uint32_t* __restrict__ sidx,
                            const uint32_t* __restrict__ fkid,
@@ -1599,28 +1583,22 @@ __global__ void k_epermute(const uint32_t* __restrict__ counter2,
                            const uint8_t* __restrict__ oflags,
                            char* __restrict__ out) {
     const uint32_t nt = *counter2;
-    int64_t* pkey = (int64_t*)out;
-    uint64_t* pcnt = (uint64_t*)(out + (size_t)nt * 8);
-    double* pmin = (double*)(out + (size_t)nt * 16);
-    double* pmax = (double*)(out + (size_t)nt * 24);
-    double* psum = (double*)(out + (size_t)nt * 32);
-    double* pavg = (double*)(out + (size_t)nt * 40);
-    uint32_t* pkid = (uint32_t*)(out + (size_t)nt * 48);
-    uint8_t* pfl = (uint8_t*)(out + (size_t)nt * 52);
+    const auto o = dz::packed_cols(out, nt);
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nt;
          i += stride) {
         const uint32_t j = sidx[i];
         const uint32_t k = fkid[j];
-        pkey[i] = (int64_t)k;
-        pcnt[i] = ocnt[j];
-        pmin[i] = omin[j];
-        pmax[i] = omax[j];
-        psum[i] = osum[j];
-        pavg[i] = oavg[j];
-        pkid[i] = k;
-        pfl[i] = oflags[j] & 1; /* packed validity is already 0/1 so the
-                                 * host build can take it verbatim */
+        o.key[i] = (int64_t)k;
+        o.cnt[i] = ocnt[j];
+        o.min[i] = omin[j];
+        o.max[i] = omax[j];
+        o.sum[i] = osum[j];
+        o.avg[i] = oavg[j];
+        o.kid[i] = k;
+        o.flags[i] = oflags[j] & 1; /* packed validity is 0/1 so the host
+                                     * build can take it verbatim (k_egather
+                                     * sets bit 1 too; k_egf writes 0/1) */
     }
 }
 
@@ -2416,8 +2394,6 @@ __global__ __launch_bounds__(BLOCK) void k_egf(const uint64_t* s_base,
     const double* f_sum = (const double*)(sl + 4 * kcap);
     __shared__ uint32_t base;
     __shared__ uint32_t wsum[WAVES_PER_BLOCK];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t k0 = (int64_t)blockIdx.x * blockDim.x; k0 < K; k0 += stride) {
         const int64_t k = k0 + threadIdx.x;
@@ -2426,51 +2402,13 @@ __global__ __launch_bounds__(BLOCK) void k_egf(const uint64_t* s_base,
         uint64_t cnt = 0;
         if (pass) {
             cnt = f_cnt[k];
-            if (ef.on) {
-                const bool valid = cnt > 0;
-                double v = 0.0;
-                bool fv = true;
-                switch (ef.field) {
-                    case 0: v = (double)cnt; break;
-                    case 1: v = valid ? f_min[k] : 0.0; fv = valid; break;
-                    case 2: v = valid ? f_max[k] : 0.0; fv = valid; break;
-                    case 3: v = valid ? f_sum[k] : 0.0; fv = valid; break;
-                    default:
-                        v = valid ? f_sum[k] / (double)cnt : 0.0;
-                        fv = valid;
-                        break;
-                }
-                if (!fv) {
-                    pass = false; /* NULL never passes a comparison filter */
-                } else {
-                    switch (ef.cmp) {
-                        case 0: pass = v < ef.lit; break;
-                        case 1: pass = v <= ef.lit; break;
-                        case 2: pass = v > ef.lit; break;
-                        case 3: pass = v >= ef.lit; break;
-                        case 4: pass = v == ef.lit; break;
-                        default: pass = v != ef.lit; break;
-                    }
-                }
-            }
+            if (ef.on)
+                pass = slab_filter_pass(ef, cnt, f_min, f_max, f_sum, k);
         }
-        const uint64_t m = __ballot(pass);
-        const uint64_t below = (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
-        const uint32_t wrank = (uint32_t)__popcll(m & below) - (pass ? 1 : 0);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t wbase = 0, tot = 0;
-        for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-            if (w < wave) wbase += wsum[w];
-            tot += wsum[w];
-        }
-        if (threadIdx.x == 0) {
-            base = tot ? atomicAdd(gtot, tot) : 0u;
-            if (tot) atomicAdd(&gcnt[c], tot);
-        }
-        __syncthreads();
+        uint32_t tot;
+        const uint32_t p = block_compact_pos(pass, gtot, wsum, &base, &tot);
+        if (threadIdx.x == 0 && tot) atomicAdd(&gcnt[c], tot);
         if (pass) {
-            const uint32_t p = base + wbase + wrank;
             const bool valid = cnt > 0;
             gkeys[p] = ((uint64_t)c << cshift) | (f - slots.base[c]);
             gkid[p] = (uint32_t)k;
@@ -2483,38 +2421,6 @@ __global__ __launch_bounds__(BLOCK) void k_egf(const uint64_t* s_base,
             gflags[p] = valid ? 1 : 0;
         }
         __syncthreads();
-    }
-}
-
-/* pack the sorted group into close-major 53 B/row columns (same layout as
- * k_epermute but keyed off the composite-sorted permutation) */
-__global__ void k_egpermute(const uint32_t* gtot, const uint32_t* sidx,
-                            const uint32_t* gkid, const uint64_t* gcnt_col,
-                            const double* gmin, const double* gmax,
-                            const double* gsum, const double* gavg,
-                            const uint8_t* gflags, char* out) {
-    const uint32_t nt = *gtot;
-    int64_t* pkey = (int64_t*)out;
-    uint64_t* pcnt = (uint64_t*)(out + (size_t)nt * 8);
-    double* pmin = (double*)(out + (size_t)nt * 16);
-    double* pmax = (double*)(out + (size_t)nt * 24);
-    double* psum = (double*)(out + (size_t)nt * 32);
-    double* pavg = (double*)(out + (size_t)nt * 40);
-    uint32_t* pkid = (uint32_t*)(out + (size_t)nt * 48);
-    uint8_t* pfl = (uint8_t*)(out + (size_t)nt * 52);
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nt;
-         i += stride) {
-        const uint32_t j = sidx[i];
-        const uint32_t k = gkid[j];
-        pkey[i] = (int64_t)k;
-        pcnt[i] = gcnt_col[j];
-        pmin[i] = gmin[j];
-        pmax[i] = gmax[j];
-        psum[i] = gsum[j];
-        pavg[i] = gavg[j];
-        pkid[i] = k;
-        pfl[i] = gflags[j];
     }
 }
 
@@ -2548,7 +2454,9 @@ void launch_emission_group_sort(hipStream_t s, int64_t elem_cap, int gcount,
     launch_emission_sort(s, elem_cap, gkeys, gskeys, giota, gokid, gtot,
                          rhist, roffs, max_key);
     int pb = (int)std::min<int64_t>((elem_cap + BLOCK - 1) / BLOCK, 2048);
-    hipLaunchKernelGGL(k_egpermute, dim3(pb), dim3(BLOCK), 0, s, gtot, giota,
+    /* pack the sorted group close-major: the per-close permute kernel,
+     * keyed off the composite-sorted permutation */
+    hipLaunchKernelGGL(k_epermute, dim3(pb), dim3(BLOCK), 0, s, gtot, giota,
                        gkid, gcnt_col, gmin, gmax, gsum, gavg, gflags, pout);
 }
 

@@ -349,7 +349,7 @@ struct dz_window_op {
         uint64_t* ocnt;
         double* omin; double* omax; double* osum; double* oavg;
         uint8_t* oflags;
-        char* pout;  /* permuted, packed final-order columns (53 B/entry) */
+        char* pout;  /* permuted, packed final-order rows (dz::packed_cols) */
     };
     DevEmit e_dev[E_POOL];
     uint64_t* e_slabs[E_POOL] = {}; /* pinned output staging per slot */
@@ -433,7 +433,7 @@ struct dz_window_op {
         uint8_t* gflags;
         uint32_t* ctr;    /* [0]=total, [1..16]=per-close counts */
         uint32_t* rhist; uint32_t* roffs;
-        char* pout;       /* packed 53 B/elem, close-major sorted */
+        char* pout;       /* packed rows (dz::packed_cols), close-major sorted */
     };
     static constexpr int E_GD = 4; /* groups in flight (one per
                                     * emission stream) */
@@ -451,9 +451,9 @@ struct dz_window_op {
     std::mutex out_mtx;             /* guards outq */
 
     /* filter pushdown */
-    bool has_filter = false;
-    int32_t f_idx = 0, f_cmp = 0;
-    double f_lit = 0.0;
+    dz::EmitFilter filter{0, 4, 0, 0.0}; /* built once by set_filter */
+    int32_t f_idx = 0; /* the filtered aggregate (variance family: the host
+                        * build finalises it before comparing) */
 
     /* output */
     std::deque<OutBuf> outq;
@@ -483,11 +483,6 @@ static void emit_worker_main(dz_window_op* op);
 static dz_status ensure_emission(dz_window_op* op);
 static dz_status process_pending(dz_window_op* op);
 static dz_status intern_sync_mirror(dz_window_op* op);
-static void build_emission_slice(dz_window_op* op, int64_t wstart,
-                                 int64_t wend, uint32_t total, uint32_t off,
-                                 uint32_t n, const char* p, OutBuf* out);
-static void build_emission_slice_views(dz_window_op* op, int64_t wstart,
-                                       int64_t wend, uint32_t n, OutBuf* out);
 
 static hipEvent_t get_event(dz_window_op* op) {
     if (!op->ev_pool.empty()) {
@@ -813,43 +808,68 @@ extern "C" const char* dz_last_error(dz_window_op* op) {
 /* ------------------------------------------------------------------ */
 
 
-static bool filter_pass(dz_window_op* op, int64_t row_cnt,
-                        double vmin, double vmax, double vsum, double vm2,
-                        bool valid) {
-    if (!op->has_filter) return true;
-    double v;
+static bool filter_pass(dz_window_op* op, uint64_t row_cnt,
+                        double vmin, double vmax, double vsum, double vm2) {
+    const dz::EmitFilter& ef = op->filter;
+    if (!ef.on) return true;
     dz_agg_op o = op->aggs[op->f_idx].op;
-    if (o == DZ_AGG_COUNT) {
-        v = (double)row_cnt;
-    } else if (is_var_op(o)) {
-        /* the comparison runs on the finalised value; NULL never passes */
-        if (dz_debug_var_finalize(o, (uint64_t)row_cnt, vm2, &v) != 1)
-            return false;
-    } else {
-        if (!valid) return false; /* NULL never passes a comparison filter */
-        switch (o) {
-            case DZ_AGG_MIN: v = vmin; break;
-            case DZ_AGG_MAX: v = vmax; break;
-            case DZ_AGG_SUM: v = vsum; break;
-            case DZ_AGG_AVG: v = vsum / (double)row_cnt; break;
-            default: v = 0; break;
-        }
+    if (!is_var_op(o)) {
+        /* a comparator code outside 0..5 passes every non-NULL group here,
+         * while the device chains compare it as != (emit_filter_pass's
+         * default arm): both long-standing, kept apart on purpose */
+        if ((uint32_t)ef.cmp > 5) return ef.field == 0 || row_cnt > 0;
+        return dz::emit_filter_pass(ef, row_cnt, vmin, vmax, vsum);
     }
-    switch (op->f_cmp) {
-        case 0: return v < op->f_lit;
-        case 1: return v <= op->f_lit;
-        case 2: return v > op->f_lit;
-        case 3: return v >= op->f_lit;
-        case 4: return v == op->f_lit;
-        case 5: return v != op->f_lit;
+    /* the comparison runs on the finalised value; NULL never passes */
+    double v;
+    if (dz_debug_var_finalize(o, row_cnt, vm2, &v) != 1) return false;
+    switch (ef.cmp) {
+        case 0: return v < ef.lit;
+        case 1: return v <= ef.lit;
+        case 2: return v > ef.lit;
+        case 3: return v >= ef.lit;
+        case 4: return v == ef.lit;
+        case 5: return v != ef.lit;
         default: return true;
+    }
+}
+
+/* Materialise the key column of `n` emitted rows from their dense ids
+ * (`ids[i]`, any integer type): utf8 offsets+data or int64 values through
+ * the ChunkedDict dictionaries (indices < the job's n_keys snapshot), or
+ * the ids themselves for dense keys — unless `dense_is_view`, where poll()
+ * serves the packed span's own key column. Global aggregates have no group
+ * column (create_schema with empty group exprs, streaming_window.rs:1096+). */
+template <typename Id>
+static void build_keys(dz_window_op* op, const Id* ids, size_t n, OutBuf& ob,
+                       bool dense_is_view) {
+    if (op->no_group) return;
+    if (op->key_kind == DZ_KEY_UTF8) {
+        ob.key_offsets.resize(n + 1);
+        ob.key_offsets[0] = 0;
+        size_t total = 0;
+        for (size_t i = 0; i < n; i++) total += op->dict_strs[ids[i]].size();
+        ob.key_data.resize(total);
+        size_t pos = 0;
+        for (size_t i = 0; i < n; i++) {
+            const std::string& s = op->dict_strs[ids[i]];
+            memcpy(ob.key_data.data() + pos, s.data(), s.size());
+            pos += s.size();
+            ob.key_offsets[i + 1] = (int32_t)pos;
+        }
+    } else if (op->key_kind == DZ_KEY_INT64) {
+        ob.key_i64.resize(n);
+        for (size_t i = 0; i < n; i++) ob.key_i64[i] = op->dict_vals[ids[i]];
+    } else if (!dense_is_view) {
+        ob.key_i64.resize(n);
+        for (size_t i = 0; i < n; i++) ob.key_i64[i] = (int64_t)ids[i];
     }
 }
 
 /* Build one emitted batch from a pinned copy of a slot slab
  * ([cnt][first][min][max][sum], each `kcap` 8-byte entries; variance-
  * declaring ops append [m2] from the side slab). Runs on the
- * emission worker thread: touches only immutable config, the deque-backed
+ * emission worker thread: touches only immutable config, the ChunkedDict
  * dictionaries (indices < the job's n_keys snapshot) and the slab. */
 static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                            int64_t K, int64_t kcap, const uint64_t* slab,
@@ -892,9 +912,8 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     rows.reserve(touched.size());
     for (auto& p : touched) {
         int32_t k = p.second;
-        int64_t cnt = (int64_t)f_cnt[k];
-        if (filter_pass(op, cnt, f_min[k], f_max[k], f_sum[k],
-                        f_m2 ? f_m2[k] : 0.0, cnt > 0))
+        if (filter_pass(op, f_cnt[k], f_min[k], f_max[k], f_sum[k],
+                        f_m2 ? f_m2[k] : 0.0))
             rows.push_back(k);
     }
     size_t n = rows.size(), na = op->aggs.size();
@@ -903,26 +922,7 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     ob.agg_i64.resize(na);
     ob.agg_f64.resize(na);
     if (op->has_var) ob.agg_valid_a.resize(na);
-    if (op->key_kind == DZ_KEY_UTF8) {
-        ob.key_offsets.resize(n + 1);
-        ob.key_offsets[0] = 0;
-        size_t total = 0;
-        for (size_t i = 0; i < n; i++) total += op->dict_strs[rows[i]].size();
-        ob.key_data.resize(total);
-        size_t pos = 0;
-        for (size_t i = 0; i < n; i++) {
-            const std::string& s = op->dict_strs[rows[i]];
-            memcpy(ob.key_data.data() + pos, s.data(), s.size());
-            pos += s.size();
-            ob.key_offsets[i + 1] = (int32_t)pos;
-        }
-    } else if (op->key_kind == DZ_KEY_INT64) {
-        ob.key_i64.resize(n);
-        for (size_t i = 0; i < n; i++) ob.key_i64[i] = op->dict_vals[rows[i]];
-    } else {
-        ob.key_i64.resize(n);
-        for (size_t i = 0; i < n; i++) ob.key_i64[i] = rows[i];
-    }
+    build_keys(op, rows.data(), n, ob, false);
     for (size_t a = 0; a < na; a++) {
         switch (op->aggs[a].op) {
             case DZ_AGG_COUNT: {
@@ -984,80 +984,56 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     ob.view.n_rows = (int64_t)n;
 }
 
-/* Pinned emission slab layout for kcap entries (49 bytes per entry):
- * [kid u32][sidx u32][flags u8][cnt u64][min f64][max f64][sum f64][avg f64]
- * column sections; kid/cols are in COMPACT order, sidx is the sorted
- * (insertion-order) permutation of compact indices. kcap is a multiple of
- * NB=512, so every section stays 8-byte aligned. */
+/* Bytes per key-capacity entry of a per-slot pinned slab (e_slabs). A slab
+ * receives either the raw state slab of a host-built per-close emission
+ * (5 * kcap * 8 = 40 B/entry) or a per-close device chain's packed span (at
+ * most kcap rows of dz::PACKED_ROW_BYTES = 53 B); 56 covers the larger and
+ * keeps the allocation a multiple of 8. */
 static constexpr int64_t SLAB_BYTES_PER_ENTRY = 56;
+static_assert(SLAB_BYTES_PER_ENTRY >= dz::PACKED_ROW_BYTES &&
+              SLAB_BYTES_PER_ENTRY >= 5 * 8, "pinned slab too small");
 
-/* Build one emitted batch from the device-sorted, device-filtered columns
- * (insertion order already established by the GPU radix sort). Runs on the
- * emission worker pool: touches only immutable config, the deque-backed
- * dictionaries (indices < the job's n_keys snapshot) and the pinned slab. */
-static void build_emission(dz_window_op* op, int64_t wstart, int64_t wend,
-                           uint32_t nt, const uint64_t* slab, OutBuf* out,
-                           int slab_idx = -1, bool zero_copy = false) {
-    /* packed final-order columns from k_epermute (53 B/row): sequential
-     * reads only — the per-row permutation gather already ran on device.
-     * zero_copy: serve the aggregate columns (and dense keys + validity)
-     * as VIEWS into the pinned span; the OutBuf keeps the slab until the
-     * consumer's next poll. */
-    const char* p = (const char*)slab;
-    const int64_t* pkey = (const int64_t*)p;
-    const uint64_t* pcnt = (const uint64_t*)(p + (size_t)nt * 8);
-    const double* pmin = (const double*)(p + (size_t)nt * 16);
-    const double* pmax = (const double*)(p + (size_t)nt * 24);
-    const double* psum = (const double*)(p + (size_t)nt * 32);
-    const double* pavg = (const double*)(p + (size_t)nt * 40);
-    const uint32_t* pkid = (const uint32_t*)(p + (size_t)nt * 48);
-    const uint8_t* pfl = (const uint8_t*)(p + (size_t)nt * 52);
-    size_t n = nt;
+/* the packed column an aggregate reads (count is u64 bits, served as i64) */
+static const void* packed_agg_col(const dz::PackedCols& c, dz_agg_op o) {
+    switch (o) {
+        case DZ_AGG_COUNT: return c.cnt;
+        case DZ_AGG_MIN: return c.min;
+        case DZ_AGG_MAX: return c.max;
+        case DZ_AGG_SUM: return c.sum;
+        case DZ_AGG_AVG: return c.avg;
+        default: return nullptr; /* variance family: never on device paths */
+    }
+}
+
+/* Build one emitted batch from `n` packed rows (`cols` already points at the
+ * batch's first row: a whole per-close span, or one close's slice of a
+ * group span) — insertion order, filter and the per-row permutation gather
+ * all ran on device, so these are sequential reads. Runs on the emission
+ * worker pool: touches only immutable config, the ChunkedDict dictionaries
+ * and the pinned span. With `views` the aggregate columns, dense keys and
+ * validity are NOT copied: poll() serves them as views into the span, which
+ * the OutBuf holds (the worker fills ob.packed and the hold beforehand). */
+static void build_emission_packed(dz_window_op* op, int64_t wstart,
+                                  int64_t wend, const dz::PackedCols& cols,
+                                  size_t n, bool views, OutBuf* out) {
     size_t na = op->aggs.size();
     OutBuf& ob = *out;
     ob.agg_i64.resize(na);
     ob.agg_f64.resize(na);
-    if (zero_copy && n > 0) {
-        ob.packed = p;
-        ob.packed_nt = nt;
-        ob.hold_slab = slab_idx;
-    }
-    if (op->no_group) {
-        /* global aggregate: output schema has no group column
-         * (create_schema with empty group exprs, streaming_window.rs:1096+) */
-    } else if (op->key_kind == DZ_KEY_UTF8) {
-        ob.key_offsets.resize(n + 1);
-        ob.key_offsets[0] = 0;
-        size_t total = 0;
-        for (size_t i = 0; i < n; i++) total += op->dict_strs[pkid[i]].size();
-        ob.key_data.resize(total);
-        size_t pos = 0;
-        for (size_t i = 0; i < n; i++) {
-            const std::string& s = op->dict_strs[pkid[i]];
-            memcpy(ob.key_data.data() + pos, s.data(), s.size());
-            pos += s.size();
-            ob.key_offsets[i + 1] = (int32_t)pos;
+    build_keys(op, cols.kid, n, ob, views);
+    if (!views) {
+        for (size_t a = 0; a < na; a++) {
+            const void* src = packed_agg_col(cols, op->aggs[a].op);
+            if (!src) continue;
+            if (op->aggs[a].op == DZ_AGG_COUNT)
+                ob.agg_i64[a].assign((const int64_t*)src,
+                                     (const int64_t*)src + n);
+            else
+                ob.agg_f64[a].assign((const double*)src,
+                                     (const double*)src + n);
         }
-    } else if (op->key_kind == DZ_KEY_INT64) {
-        ob.key_i64.resize(n);
-        for (size_t i = 0; i < n; i++) ob.key_i64[i] = op->dict_vals[pkid[i]];
-    } else if (!ob.packed) {
-        ob.key_i64.assign(pkey, pkey + n);
+        ob.agg_valid.assign(cols.flags, cols.flags + n);
     }
-    if (!ob.packed)
-    for (size_t a = 0; a < na; a++) {
-        switch (op->aggs[a].op) {
-            case DZ_AGG_COUNT:
-                ob.agg_i64[a].assign((const int64_t*)pcnt,
-                                     (const int64_t*)pcnt + n);
-                break;
-            case DZ_AGG_MIN: ob.agg_f64[a].assign(pmin, pmin + n); break;
-            case DZ_AGG_MAX: ob.agg_f64[a].assign(pmax, pmax + n); break;
-            case DZ_AGG_SUM: ob.agg_f64[a].assign(psum, psum + n); break;
-            case DZ_AGG_AVG: ob.agg_f64[a].assign(pavg, pavg + n); break;
-        }
-    }
-    if (!ob.packed) ob.agg_valid.assign(pfl, pfl + n);
     ob.wstart.assign(n, wstart);
     ob.wend.assign(n, wend);
     ob.view.n_rows = (int64_t)n;
@@ -1167,11 +1143,12 @@ static void emit_worker_main(dz_window_op* op) {
                     if (ctl.span >= 0) {
                         dst = op->e_gpin[ctl.span];
                     } else {
-                        ctl.heap = (char*)malloc((size_t)gtot * 53);
+                        ctl.heap = (char*)malloc((size_t)gtot * dz::PACKED_ROW_BYTES);
                         dst = ctl.heap;
                     }
                     hipMemcpy(dst, op->e_gd[job.gbuf].pout,
-                              (size_t)gtot * 53, hipMemcpyDeviceToHost);
+                              (size_t)gtot * dz::PACKED_ROW_BYTES,
+                              hipMemcpyDeviceToHost);
                 }
                 ctl.gtot = gtot;
                 ctl.ready.store(true, std::memory_order_release);
@@ -1190,11 +1167,10 @@ static void emit_worker_main(dz_window_op* op) {
                 ob.packed_nt = ctl.gtot;
                 ob.packed_off = off;
                 ob.hold_group = job.ctl;
-                build_emission_slice_views(op, job.wstart, job.wend, cnt, &ob);
-            } else {
-                build_emission_slice(op, job.wstart, job.wend, ctl.gtot, off,
-                                     cnt, src, &ob);
             }
+            build_emission_packed(op, job.wstart, job.wend,
+                                  dz::packed_cols(src, ctl.gtot, off), cnt,
+                                  zc, &ob);
         } else if (job.device) {
             /* copy exactly nt2 packed rows (the filter already ran on
              * device, so this is the final output volume, not the keyspace) */
@@ -1206,7 +1182,7 @@ static void emit_worker_main(dz_window_op* op) {
                  * packed every final-order column: ONE contiguous pull */
                 hipStream_t wcs = op->c_streams[job.cs];
                 hipError_t e = hipMemcpyAsync(op->e_slabs[job.slab], d.pout,
-                                              (size_t)nt * 53,
+                                              (size_t)nt * dz::PACKED_ROW_BYTES,
                                               hipMemcpyDeviceToHost, wcs);
                 if (e == hipSuccess) e = hipEventRecord(job.ev, wcs);
                 if (e != hipSuccess) {
@@ -1230,8 +1206,16 @@ static void emit_worker_main(dz_window_op* op) {
                 zc = op->e_free.size() >= 8;
                 gen = op->e_slab_gen;
             }
-            build_emission(op, job.wstart, job.wend, nt,
-                           op->e_slabs[job.slab], &ob, job.slab, zc);
+            /* zero-copy (nt >= 16384 here): the OutBuf keeps the slab until
+             * the consumer's next poll */
+            const char* span = (const char*)op->e_slabs[job.slab];
+            if (zc) {
+                ob.packed = span;
+                ob.packed_nt = nt;
+                ob.hold_slab = job.slab;
+            }
+            build_emission_packed(op, job.wstart, job.wend,
+                                  dz::packed_cols(span, nt), nt, zc, &ob);
             ob.slab_gen = gen;
             (zc ? op->e_zc_builds : op->e_copy_builds)++;
         } else {
@@ -1308,8 +1292,16 @@ static dz_status ensure_emission(dz_window_op* op) {
         for (int i = 0; i < dz_window_op::E_POOL; i++) {
             auto& d = op->e_dev[i];
             hipFree(d.base);
-            /* 3x u64 keys + 5x u64/f64 columns + 4x u32 + flags + counters
-             * + the 53 B/entry packed permuted-output block */
+            constexpr size_t per_entry =
+                3 * 8 +                 /* ekeys, fkeys, skeys */
+                5 * 8 +                 /* ocnt, omin, omax, osum, oavg */
+                4 * 4 +                 /* ekid, fkid, fiota, okid */
+                1 +                     /* oflags */
+                dz::PACKED_ROW_BYTES;   /* pout */
+            constexpr size_t fixed = 64; /* counter cells */
+            /* the parts come to 134 B/entry + 64 B; the allocation has
+             * always been 140 B/entry + 128 B and keeps that slack */
+            static_assert(per_entry <= 140 && fixed <= 128, "DevEmit carve");
             CHK(op, hipMalloc(&d.base, (size_t)kc * 140 + 128));
             char* p = d.base;
             d.ekeys = (uint64_t*)p; p += kc * 8;
@@ -1377,7 +1369,8 @@ static dz_status ensure_gd(dz_window_op* op) {
     const int64_t nblk = (E + dz::EMIT_RCHUNK - 1) / dz::EMIT_RCHUNK;
     for (int i = 0; i < dz_window_op::E_GD; i++) {
         auto& g = op->e_gd[i];
-        size_t bytes = (size_t)E * (8 + 8 + 4 + 4 + 4 + 8 + 32 + 1 + 53) +
+        size_t bytes = (size_t)E * (8 + 8 + 4 + 4 + 4 + 8 + 32 + 1 +
+                                   dz::PACKED_ROW_BYTES) +
                        (size_t)(nblk + 17 + nblk) * dz::EMIT_RBINS * 4 + 256;
         CHK(op, hipMalloc(&g.base, bytes));
         char* p = g.base;
@@ -1396,7 +1389,8 @@ static dz_status ensure_gd(dz_window_op* op) {
         g.gflags = (uint8_t*)p; p += E;
         g.ctr = (uint32_t*)p; p += 128;
         g.pout = p;
-        CHK(op, hipHostMalloc((void**)&op->e_gpin[i], (size_t)E * 53));
+        CHK(op, hipHostMalloc((void**)&op->e_gpin[i],
+                              (size_t)E * dz::PACKED_ROW_BYTES));
     }
     CHK(op, hipHostMalloc((void**)&op->e_gpcnt,
                           (size_t)dz_window_op::E_GD * 32 * 4));
@@ -1411,412 +1405,234 @@ static dz_status ensure_gd(dz_window_op* op) {
     return DZ_OK;
 }
 
-/* Build one close's slice of a group-batched packed span (close-major,
- * insertion-ordered): total = the group's element count (column-section
- * stride), [off, off+n) = this close's rows. Materialising build — the
- * group path runs in the many-SMALL-closes regime by construction. */
-static void build_emission_slice(dz_window_op* op, int64_t wstart,
-                                 int64_t wend, uint32_t total, uint32_t off,
-                                 uint32_t n, const char* p, OutBuf* out) {
-    const int64_t* pkey = (const int64_t*)p + off;
-    const uint64_t* pcnt = (const uint64_t*)(p + (size_t)total * 8) + off;
-    const double* pmin = (const double*)(p + (size_t)total * 16) + off;
-    const double* pmax = (const double*)(p + (size_t)total * 24) + off;
-    const double* psum = (const double*)(p + (size_t)total * 32) + off;
-    const double* pavg = (const double*)(p + (size_t)total * 40) + off;
-    const uint32_t* pkid = (const uint32_t*)(p + (size_t)total * 48) + off;
-    const uint8_t* pfl = (const uint8_t*)(p + (size_t)total * 52) + off;
-    size_t na = op->aggs.size();
-    OutBuf& ob = *out;
-    ob.agg_i64.resize(na);
-    ob.agg_f64.resize(na);
-    if (op->no_group) {
-    } else if (op->key_kind == DZ_KEY_UTF8) {
-        ob.key_offsets.resize(n + 1);
-        ob.key_offsets[0] = 0;
-        size_t totalb = 0;
-        for (size_t i = 0; i < n; i++) totalb += op->dict_strs[pkid[i]].size();
-        ob.key_data.resize(totalb);
-        size_t pos = 0;
-        for (size_t i = 0; i < n; i++) {
-            const std::string& str = op->dict_strs[pkid[i]];
-            memcpy(ob.key_data.data() + pos, str.data(), str.size());
-            pos += str.size();
-            ob.key_offsets[i + 1] = (int32_t)pos;
-        }
-    } else if (op->key_kind == DZ_KEY_INT64) {
-        ob.key_i64.resize(n);
-        for (size_t i = 0; i < n; i++) ob.key_i64[i] = op->dict_vals[pkid[i]];
-    } else {
-        ob.key_i64.assign(pkey, pkey + n);
+/* ---- trigger_windows and its three enqueue strategies ---------------- */
+
+struct Closed { int64_t start, end; int32_t slot; uint64_t base; };
+
+/* an emission event from the pool, or a fresh one (e_mtx held) */
+static hipEvent_t take_event(dz_window_op* op) {
+    if (!op->e_ev_pool.empty()) {
+        hipEvent_t e = op->e_ev_pool.back();
+        op->e_ev_pool.pop_back();
+        return e;
     }
-    for (size_t a = 0; a < na; a++) {
-        switch (op->aggs[a].op) {
-            case DZ_AGG_COUNT:
-                ob.agg_i64[a].assign((const int64_t*)pcnt,
-                                     (const int64_t*)pcnt + n);
-                break;
-            case DZ_AGG_MIN: ob.agg_f64[a].assign(pmin, pmin + n); break;
-            case DZ_AGG_MAX: ob.agg_f64[a].assign(pmax, pmax + n); break;
-            case DZ_AGG_SUM: ob.agg_f64[a].assign(psum, psum + n); break;
-            case DZ_AGG_AVG: ob.agg_f64[a].assign(pavg, pavg + n); break;
-        }
-    }
-    ob.agg_valid.assign(pfl, pfl + n);
-    ob.wstart.assign(n, wstart);
-    ob.wend.assign(n, wend);
-    ob.view.n_rows = (int64_t)n;
+    hipEvent_t e;
+    hipEventCreate(&e);
+    return e;
 }
 
-/* Zero-copy slice build: the aggregate columns (and dense keys +
- * validity) are served by poll() as views into the group span at
- * packed_off; only dictionary-encoded keys materialize here. */
-static void build_emission_slice_views(dz_window_op* op, int64_t wstart,
-                                       int64_t wend, uint32_t n, OutBuf* out) {
-    OutBuf& ob = *out;
-    const char* p = ob.packed;
-    const uint32_t total = ob.packed_nt;
-    const uint32_t* pkid =
-        (const uint32_t*)(p + (size_t)total * 48) + ob.packed_off;
-    size_t na = op->aggs.size();
-    ob.agg_i64.resize(na);
-    ob.agg_f64.resize(na);
-    if (op->no_group) {
-    } else if (op->key_kind == DZ_KEY_UTF8) {
-        ob.key_offsets.resize(n + 1);
-        ob.key_offsets[0] = 0;
-        size_t totalb = 0;
-        for (size_t i = 0; i < n; i++) totalb += op->dict_strs[pkid[i]].size();
-        ob.key_data.resize(totalb);
-        size_t pos = 0;
-        for (size_t i = 0; i < n; i++) {
-            const std::string& str = op->dict_strs[pkid[i]];
-            memcpy(ob.key_data.data() + pos, str.data(), str.size());
-            pos += str.size();
-            ob.key_offsets[i + 1] = (int32_t)pos;
-        }
-    } else if (op->key_kind == DZ_KEY_INT64) {
-        ob.key_i64.resize(n);
-        for (size_t i = 0; i < n; i++) ob.key_i64[i] = op->dict_vals[pkid[i]];
-    } /* dense: the key column is a view (poll) */
-    ob.wstart.assign(n, wstart);
-    ob.wend.assign(n, wend);
-    ob.view.n_rows = (int64_t)n;
+/* the next rotating slot-release frontier event (see e_frontier) */
+static hipEvent_t next_frontier(dz_window_op* op) {
+    hipEvent_t& fr = op->e_frontier[op->e_frontier_idx];
+    if (!fr) hipEventCreateWithFlags(&fr, hipEventDisableTiming);
+    op->e_frontier_idx = (op->e_frontier_idx + 1) % dz_window_op::E_FRONTIERS;
+    return fr;
 }
 
-/* trigger_windows (grouped_window_agg_stream.rs:220-253): closed windows are
- * copied D2H asynchronously and built by the worker thread off the push
- * critical path; dz_window_op_drain/finish wait for completion. */
-static dz_status trigger_windows(dz_window_op* op) {
-    if (!op->has_wm) return DZ_OK;
-    struct Closed { int64_t start, end; int32_t slot; uint64_t base; };
-    std::vector<Closed> closed;
-    for (auto it = op->open.begin(); it != op->open.end();) {
-        if (op->watermark >= it->second.end) {
-            closed.push_back({it->first, it->second.end, it->second.slot,
-                              it->second.row_base});
-            it = op->open.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    if (closed.empty()) return DZ_OK;
-    if (ensure_emission(op) != DZ_OK) return DZ_ERR;
-    size_t stride = (size_t)op->kcap * 5;
-    HostTimer ht(op, "h_emit_enqueue");
-    /* emission kernels run on the copy stream AFTER the compute stream's
-     * folds for these slots */
-    hipEvent_t evA;
+/* one close's job with what every strategy fills (e_mtx held: the ticket
+ * fixes the output order); a raw-slab host build unless the caller says
+ * otherwise */
+static dz_window_op::EmitJob make_job(dz_window_op* op, const Closed& c,
+                                      hipEvent_t ev) {
+    dz_window_op::EmitJob j;
+    j.ev = ev;
+    j.slab = -1;
+    j.wstart = c.start;
+    j.wend = c.end;
+    j.n_keys = op->n_keys;
+    j.kcap = op->kcap;
+    j.ticket = op->e_ticket_next++;
+    j.device = false;
+    return j;
+}
+
+/* group-batched device path: a whole trigger group of SMALL closes in ONE
+ * chain (~25 host enqueues total instead of per close — the push-thread
+ * enqueue serialization was the cfg3 sliding wall). Worst-case safe: the
+ * caller caps gcount so gcount * kcap <= E_GELEMS — the fused gather cannot
+ * overflow. */
+static dz_status enqueue_group_device(dz_window_op* op, const Closed* cl,
+                                      int gcount) {
+    if (ensure_gd(op) != DZ_OK) return DZ_ERR;
+    int gdidx;
+    hipEvent_t gev;
     {
+        HostTimer htw(op, "h_emit_slabwait");
+        std::unique_lock<std::mutex> lk(op->e_mtx);
+        op->e_cv.wait(lk, [&] { return !op->e_gdfree.empty(); });
+        gdidx = op->e_gdfree.back();
+        op->e_gdfree.pop_back();
+        gev = take_event(op);
+    }
+    auto& gd = op->e_gd[gdidx];
+    hipStream_t cs = op->c_streams[gdidx % dz_window_op::E_CSTREAMS];
+    dz::EGatherSlots gs;
+    hipEvent_t fr = next_frontier(op);
+    uint64_t max_first = 1;
+    for (int i = 0; i < gcount; i++) {
+        gs.s[i] = cl[i].slot;
+        gs.base[i] = cl[i].base;
+        max_first = std::max(max_first, op->rows_seen - cl[i].base);
+        op->free_slots.push_back({cl[i].slot, fr, false});
+    }
+    /* composite sort key = close_idx << cshift | (first - base); the
+     * rebased first is bounded by the window's row span, so cshift
+     * stays ~24-34 bits at any stream age */
+    const int cshift = 64 - __builtin_clzll(max_first);
+    {
+        HostTimer htg(op, "h_trig_gather");
+        CHK(op, hipMemsetAsync(gd.ctr, 0, 128, cs));
+        dz::launch_emission_group_read(cs, op->s_base, op->kcap * 5, gs,
+                                       gcount, op->n_keys, op->kcap,
+                                       op->filter, cshift, gd.gkeys, gd.gkid,
+                                       gd.giota, gd.gcnt_col, gd.gmin,
+                                       gd.gmax, gd.gsum, gd.gavg, gd.gflags,
+                                       gd.ctr, gd.ctr + 1);
+        CHK(op, hipEventRecord(fr, cs)); /* slabs fully read */
+        dz::launch_emission_group_sort(cs, dz_window_op::E_GELEMS, gcount,
+                                       cshift, max_first, gd.gkeys,
+                                       gd.gskeys, gd.gkid, gd.gokid,
+                                       gd.giota, gd.gcnt_col, gd.gmin,
+                                       gd.gmax, gd.gsum, gd.gavg,
+                                       gd.gflags, gd.ctr, gd.rhist,
+                                       gd.roffs, gd.pout);
+        CHK(op, hipMemcpyAsync(op->e_gpcnt + 32 * gdidx, gd.ctr, 128,
+                               hipMemcpyDeviceToHost, cs));
+        CHK(op, hipEventRecord(gev, cs));
+    }
+    auto left = std::make_shared<std::atomic<int>>(gcount);
+    auto ctl = std::make_shared<GroupCtl>();
+    {
+        HostTimer htj(op, "h_trig_jobs");
         std::lock_guard<std::mutex> lk(op->e_mtx);
-        if (!op->e_ev_pool.empty()) {
-            evA = op->e_ev_pool.back();
-            op->e_ev_pool.pop_back();
+        for (int i = 0; i < gcount; i++) {
+            dz_window_op::EmitJob j = make_job(op, cl[i], gev);
+            j.device = true;
+            j.grouped = true;
+            j.gbuf = gdidx;
+            j.goff = i;
+            j.grp_left = left;
+            j.ctl = ctl;
+            op->e_jobs.push_back(std::move(j));
+            op->e_inflight++;
+        }
+    }
+    op->e_cv.notify_all();
+    return DZ_OK;
+}
+
+/* host-built closes with pinned group buffers (small keyspaces, and every
+ * variance-declaring op): pack the whole group's slabs with one gather
+ * launch into a pinned group buffer behind ONE shared event — the push
+ * thread pays a fixed ~4 hip calls per group instead of ~5 per close
+ * (measured ~55 µs x ~8 closes/step at cfg2) */
+static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
+                                    int gcount) {
+    hipEvent_t gev;
+    int gbuf;
+    {
+        HostTimer htw(op, "h_emit_slabwait");
+        std::unique_lock<std::mutex> lk(op->e_mtx);
+        op->e_cv.wait(lk, [&] { return !op->e_gfree.empty(); });
+        gbuf = op->e_gfree.back();
+        op->e_gfree.pop_back();
+        gev = take_event(op);
+    }
+    dz::EGatherSlots gs;
+    /* slots are readable again once the gather (not the D2H) is done:
+     * gate their reuse on the next rotating frontier event */
+    hipEvent_t fr = next_frontier(op);
+    for (int i = 0; i < gcount; i++) {
+        gs.s[i] = cl[i].slot;
+        op->free_slots.push_back({cl[i].slot, fr, false});
+    }
+    {
+        /* ONE launch reads the closing slots and writes their slabs
+         * straight into the pinned group buffer over the host link —
+         * fully asynchronous for the push thread (hipMemcpyAsync D2H
+         * was measured performing the transfer at ENQUEUE time) */
+        HostTimer htg(op, "h_trig_gather");
+        if (op->has_var) {
+            if ((int64_t)gcount * 6 * op->kcap > op->e_gbuf_cells) {
+                op->err = "internal: emission group of " +
+                          std::to_string(gcount) + " closes x " +
+                          std::to_string(op->kcap) +
+                          " keys overflows the pinned group buffer";
+                return DZ_ERR;
+            }
+            dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
+                                         op->v_base, op->kcap, gs, gcount,
+                                         op->e_gbufs_dev[gbuf]);
         } else {
-            hipEventCreate(&evA);
+            dz::launch_egather_slabs(op->copy_stream, op->s_base,
+                                     op->kcap * 5, gs, gcount,
+                                     op->e_gbufs_dev[gbuf]);
         }
+        CHK(op, hipEventRecord(fr, op->copy_stream));
+        CHK(op, hipEventRecord(gev, op->copy_stream));
     }
+    auto left = std::make_shared<std::atomic<int>>(gcount);
     {
-        HostTimer htf(op, "h_trig_fence");
-        CHK(op, hipEventRecord(evA, op->stream));
-        for (int s = 0; s < dz_window_op::E_CSTREAMS; s++)
-            CHK(op, hipStreamWaitEvent(op->c_streams[s], evA, 0));
-    }
-    {
+        HostTimer htj(op, "h_trig_jobs");
         std::lock_guard<std::mutex> lk(op->e_mtx);
-        op->e_ev_pool.push_back(evA);
-    }
-    dz::EmitFilter ef;
-    ef.on = op->has_filter ? 1 : 0;
-    ef.cmp = op->f_cmp;
-    ef.lit = op->f_lit;
-    ef.field = 4;
-    if (op->has_filter) {
-        switch (op->aggs[op->f_idx].op) {
-            case DZ_AGG_COUNT: ef.field = 0; break;
-            case DZ_AGG_MIN: ef.field = 1; break;
-            case DZ_AGG_MAX: ef.field = 2; break;
-            case DZ_AGG_SUM: ef.field = 3; break;
-            default: ef.field = 4; break;
+        for (int i = 0; i < gcount; i++) {
+            dz_window_op::EmitJob j = make_job(op, cl[i], gev);
+            j.grp_left = left;
+            j.gbuf = gbuf;
+            j.goff = i;
+            op->e_jobs.push_back(std::move(j));
+            op->e_inflight++;
         }
     }
-    /* Two phases per GROUP of closes: slab readers (compact+gather) for the
-     * whole group first, so the slot-release events precede the group's
-     * sorts/copies on the copy stream — window slots come back to the
-     * compute stream right after its folds, not behind emission work.
-     * Groups are bounded by half the slab pool: phase 1 must never wait for
-     * slabs whose release depends on this group's phase 2 (deadlock). */
+    op->e_cv.notify_all();
+    return DZ_OK;
+}
+
+/* per-close chains, one pool slab each: the device chain with its zero-copy
+ * large-output path (> 65536 live keys), else ONE pinned copy of the raw
+ * slab for a host build. Two phases over the group: slab readers
+ * (compact+gather) for every close first, so the slot-release events precede
+ * the group's sorts/copies on the emission streams — window slots come back
+ * to the compute stream right after its folds, not behind emission work.
+ * *g1c = the closes actually enqueued (<= gcount, see LIVENESS). */
+static dz_status enqueue_per_close(dz_window_op* op, const Closed* cl,
+                                   int gcount, int* g1c) {
     struct Pending { int slab; hipEvent_t ev; };
-    constexpr size_t EGROUP = dz_window_op::E_POOL / 2;
-    /* variance-declaring ops take the host-built path at every key count
-     * (the device chains carry no m2 column) */
-    const bool dev_path_g = op->n_keys > 65536 && !op->has_var;
-    /* group-batched device path: a whole trigger group of SMALL closes in
-     * ONE chain (~25 host enqueues total instead of per close — the
-     * push-thread enqueue serialization was the cfg3 sliding wall). Large
-     * closes (hint above the threshold) keep the per-close chain with its
-     * zero-copy large-output path. Worst-case safe: gstep is capped so
-     * gcount * kcap <= E_GELEMS — the fused gather cannot overflow. */
-    static const uint32_t group_max = [] {
-        const char* v = getenv("DZ_EMIT_GROUP_MAX");
-        return v ? (uint32_t)atoi(v) : 65536u;
-    }();
-    const bool grouped_ok = dev_path_g && op->kcap > 0 &&
-        op->kcap <= dz_window_op::E_GELEMS &&
-        op->e_nt_hint.load(std::memory_order_relaxed) <= group_max &&
-        op->batch_seq < (1u << 19);
-    size_t g0 = 0;
-    while (g0 < closed.size()) {
-    size_t gstep = EGROUP;
-    if (op->has_var)
-        gstep = std::min<size_t>(gstep, (size_t)std::max(1, op->e_gbuf_closes));
-    if (grouped_ok)
-        gstep = std::min<size_t>(gstep, std::max<size_t>(1,
-            (size_t)(dz_window_op::E_GELEMS / op->kcap)));
-    const size_t g1 = std::min(closed.size(), g0 + gstep);
-    if (grouped_ok) {
-        if (ensure_gd(op) != DZ_OK) return DZ_ERR;
-        int gdidx;
-        hipEvent_t gev;
-        {
-            HostTimer htw(op, "h_emit_slabwait");
-            std::unique_lock<std::mutex> lk(op->e_mtx);
-            op->e_cv.wait(lk, [&] { return !op->e_gdfree.empty(); });
-            gdidx = op->e_gdfree.back();
-            op->e_gdfree.pop_back();
-            if (!op->e_ev_pool.empty()) {
-                gev = op->e_ev_pool.back();
-                op->e_ev_pool.pop_back();
-            } else {
-                hipEventCreate(&gev);
-            }
-        }
-        auto& gd = op->e_gd[gdidx];
-        const int gcount = (int)(g1 - g0);
-        hipStream_t cs = op->c_streams[gdidx % dz_window_op::E_CSTREAMS];
-        dz::EGatherSlots gs;
-        hipEvent_t fr = op->e_frontier[op->e_frontier_idx];
-        if (!fr) {
-            hipEventCreateWithFlags(&fr, hipEventDisableTiming);
-            op->e_frontier[op->e_frontier_idx] = fr;
-        }
-        op->e_frontier_idx =
-            (op->e_frontier_idx + 1) % dz_window_op::E_FRONTIERS;
-        uint64_t max_first = 1;
-        for (size_t ci = g0; ci < g1; ci++) {
-            gs.s[ci - g0] = closed[ci].slot;
-            gs.base[ci - g0] = closed[ci].base;
-            max_first = std::max(max_first,
-                                 op->rows_seen - closed[ci].base);
-            op->free_slots.push_back({closed[ci].slot, fr, false});
-        }
-        /* composite sort key = close_idx << cshift | (first - base); the
-         * rebased first is bounded by the window's row span, so cshift
-         * stays ~24-34 bits at any stream age */
-        const int cshift = 64 - __builtin_clzll(max_first);
-        {
-            HostTimer htg(op, "h_trig_gather");
-            CHK(op, hipMemsetAsync(gd.ctr, 0, 128, cs));
-            dz::launch_emission_group_read(cs, op->s_base, (int64_t)stride, gs,
-                                           gcount, op->n_keys, op->kcap, ef,
-                                           cshift, gd.gkeys, gd.gkid,
-                                           gd.giota, gd.gcnt_col, gd.gmin,
-                                           gd.gmax, gd.gsum, gd.gavg,
-                                           gd.gflags, gd.ctr, gd.ctr + 1);
-            CHK(op, hipEventRecord(fr, cs)); /* slabs fully read */
-            dz::launch_emission_group_sort(cs, dz_window_op::E_GELEMS, gcount,
-                                           cshift, max_first, gd.gkeys,
-                                           gd.gskeys, gd.gkid, gd.gokid,
-                                           gd.giota, gd.gcnt_col, gd.gmin,
-                                           gd.gmax, gd.gsum, gd.gavg,
-                                           gd.gflags, gd.ctr, gd.rhist,
-                                           gd.roffs, gd.pout);
-            CHK(op, hipMemcpyAsync(op->e_gpcnt + 32 * gdidx, gd.ctr, 128,
-                                   hipMemcpyDeviceToHost, cs));
-            CHK(op, hipEventRecord(gev, cs));
-        }
-        auto left = std::make_shared<std::atomic<int>>(gcount);
-        auto ctl = std::make_shared<GroupCtl>();
-        {
-            HostTimer htj(op, "h_trig_jobs");
-            std::lock_guard<std::mutex> lk(op->e_mtx);
-            for (size_t ci = g0; ci < g1; ci++) {
-                dz_window_op::EmitJob j;
-                j.ev = gev;
-                j.slab = -1;
-                j.wstart = closed[ci].start;
-                j.wend = closed[ci].end;
-                j.n_keys = op->n_keys;
-                j.kcap = op->kcap;
-                j.device = true;
-                j.grouped = true;
-                j.gbuf = gdidx;
-                j.goff = (int)(ci - g0);
-                j.grp_left = left;
-                j.ctl = ctl;
-                j.ticket = op->e_ticket_next++;
-                op->e_jobs.push_back(std::move(j));
-                op->e_inflight++;
-            }
-        }
-        op->e_cv.notify_all();
-        g0 = g1;
-        continue;
-    }
-    if (!dev_path_g && op->e_gbufs[0]) {
-        /* host-built closes (small keyspaces): pack the whole group's slabs
-         * with one gather launch + ONE D2H into a pinned group buffer behind
-         * ONE shared event — the push thread pays a fixed ~4 hip calls per
-         * group instead of ~5 per close (measured ~55 µs x ~8 closes/step
-         * at cfg2) */
-        hipEvent_t gev;
-        int gbuf;
-        {
-            HostTimer htw(op, "h_emit_slabwait");
-            std::unique_lock<std::mutex> lk(op->e_mtx);
-            op->e_cv.wait(lk, [&] { return !op->e_gfree.empty(); });
-            gbuf = op->e_gfree.back();
-            op->e_gfree.pop_back();
-            if (!op->e_ev_pool.empty()) {
-                gev = op->e_ev_pool.back();
-                op->e_ev_pool.pop_back();
-            } else {
-                hipEventCreate(&gev);
-            }
-        }
-        dz::EGatherSlots gs;
-        const int gcount = (int)(g1 - g0);
-        /* slots are readable again once the gather (not the D2H) is done:
-         * gate their reuse on the next rotating frontier event */
-        hipEvent_t fr = op->e_frontier[op->e_frontier_idx];
-        if (!fr) {
-            hipEventCreateWithFlags(&fr, hipEventDisableTiming);
-            op->e_frontier[op->e_frontier_idx] = fr;
-        }
-        op->e_frontier_idx = (op->e_frontier_idx + 1) % dz_window_op::E_FRONTIERS;
-        for (size_t ci = g0; ci < g1; ci++) {
-            gs.s[ci - g0] = closed[ci].slot;
-            op->free_slots.push_back({closed[ci].slot, fr, false});
-        }
-        {
-            /* ONE launch reads the closing slots and writes their slabs
-             * straight into the pinned group buffer over the host link —
-             * fully asynchronous for the push thread (hipMemcpyAsync D2H
-             * was measured performing the transfer at ENQUEUE time) */
-            HostTimer htg(op, "h_trig_gather");
-            if (op->has_var) {
-                if ((int64_t)gcount * 6 * op->kcap > op->e_gbuf_cells) {
-                    op->err = "internal: emission group of " +
-                              std::to_string(gcount) + " closes x " +
-                              std::to_string(op->kcap) +
-                              " keys overflows the pinned group buffer";
-                    return DZ_ERR;
-                }
-                dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
-                                             op->v_base, op->kcap, gs, gcount,
-                                             op->e_gbufs_dev[gbuf]);
-            } else
-            dz::launch_egather_slabs(op->copy_stream, op->s_base, stride, gs,
-                                     gcount, op->e_gbufs_dev[gbuf]);
-            CHK(op, hipEventRecord(fr, op->copy_stream));
-            CHK(op, hipEventRecord(gev, op->copy_stream));
-        }
-        auto left = std::make_shared<std::atomic<int>>(gcount);
-        {
-            HostTimer htj(op, "h_trig_jobs");
-            std::lock_guard<std::mutex> lk(op->e_mtx);
-            for (size_t ci = g0; ci < g1; ci++) {
-                dz_window_op::EmitJob j;
-                j.ev = gev;
-                j.slab = -1;
-                j.wstart = closed[ci].start;
-                j.wend = closed[ci].end;
-                j.n_keys = op->n_keys;
-                j.kcap = op->kcap;
-                j.device = false;
-                j.grp_left = left;
-                j.gbuf = gbuf;
-                j.goff = (int)(ci - g0);
-                j.ticket = op->e_ticket_next++;
-                op->e_jobs.push_back(std::move(j));
-                op->e_inflight++;
-            }
-        }
-        op->e_cv.notify_all();
-        g0 = g1;
-        continue;
-    }
-    if (op->has_var) {
-        /* unreachable while ensure_emission holds: the per-close staging
-         * below carries no m2 column — refuse rather than emit without it */
-        op->err = "internal: variance aggregates need the pinned group "
-                  "buffers (allocation missing)";
-        return DZ_ERR;
-    }
+    const size_t stride = (size_t)op->kcap * 5;
+    const bool dev_path = op->n_keys > 65536;
     std::vector<Pending> pend;
-    pend.reserve(g1 - g0);
+    pend.reserve(gcount);
     /* LIVENESS: a slab taken in phase 1 is dead weight until phase 2
      * pushes its job — workers can only release slabs for jobs that
      * exist. Block for the group's FIRST slab only; if the pool dries
      * mid-group, truncate the group here, run phase 2 for the slabs
-     * already taken, and continue (the outer loop re-forms the rest).
+     * already taken, and return (the caller re-forms the rest).
      * Without this, >=17 pending closes plus a zero-copy hold backlog
      * (slabs pinned until the consumer polls) deadlock the pipeline —
      * reproduced under rocprofv3's enqueue slowdown. */
-    size_t g1c = g1;
-    for (size_t ci = g0; ci < g1c; ci++) {
-        auto& c = closed[ci];
+    *g1c = gcount;
+    for (int i = 0; i < *g1c; i++) {
+        const Closed& c = cl[i];
         int slab;
         hipEvent_t ev, slot_ev;
         {
             HostTimer htw(op, "h_emit_slabwait");
             std::unique_lock<std::mutex> lk(op->e_mtx);
-            if (ci == g0) {
+            if (i == 0) {
                 op->e_cv.wait(lk, [&] { return !op->e_free.empty(); });
             } else if (op->e_free.empty()) {
-                g1c = ci;
+                *g1c = i;
                 break;
             }
             slab = op->e_free.back();
             op->e_free.pop_back();
-            auto take = [&]() -> hipEvent_t {
-                if (!op->e_ev_pool.empty()) {
-                    hipEvent_t e = op->e_ev_pool.back();
-                    op->e_ev_pool.pop_back();
-                    return e;
-                }
-                hipEvent_t e;
-                hipEventCreate(&e);
-                return e;
-            };
-            ev = take();
-            slot_ev = take();
+            ev = take_event(op);
+            slot_ev = take_event(op);
             op->e_inflight++;
         }
         dz_window_op::DevEmit& d = op->e_dev[slab];
         const uint64_t* sl = op->s_base + (size_t)c.slot * stride;
-        const bool dev_path = op->n_keys > 65536;
-        hipStream_t cs = op->c_streams[(ci - g0) % dz_window_op::E_CSTREAMS];
+        hipStream_t cs = op->c_streams[i % dz_window_op::E_CSTREAMS];
         if (!dev_path) {
             /* small keyspaces: ONE pinned copy of the raw slab; the worker
              * sorts/filters on host (15 stream ops per close would cost more
@@ -1824,32 +1640,29 @@ static dz_status trigger_windows(dz_window_op* op) {
             CHK(op, hipMemcpyAsync(op->e_slabs[slab], sl, stride * 8,
                                    hipMemcpyDeviceToHost, cs));
         } else {
-        dz::launch_zero_counters(cs, d.counter);
-        if (op->n_keys > 0) {
-            dz::launch_emission_slabread(cs,
-                                         /*first*/ sl + op->kcap,
-                                         /*cnt*/ sl,
-                                         /*min*/ (const double*)(sl + 2 * op->kcap),
-                                         /*max*/ (const double*)(sl + 3 * op->kcap),
-                                         /*sum*/ (const double*)(sl + 4 * op->kcap),
-                                         c.base, op->n_keys, d.ekeys, d.ekid, d.fkeys,
-                                         d.fkid, d.fiota, d.counter,
-                                         d.counter + 1, ef, d.ocnt, d.omin,
-                                         d.omax, d.osum, d.oavg, d.oflags);
-        }
+            dz::launch_zero_counters(cs, d.counter);
+            if (op->n_keys > 0) {
+                dz::launch_emission_slabread(
+                    cs, /*first*/ sl + op->kcap, /*cnt*/ sl,
+                    /*min*/ (const double*)(sl + 2 * op->kcap),
+                    /*max*/ (const double*)(sl + 3 * op->kcap),
+                    /*sum*/ (const double*)(sl + 4 * op->kcap), c.base,
+                    op->n_keys, d.ekeys, d.ekid, d.fkeys, d.fkid, d.fiota,
+                    d.counter, d.counter + 1, op->filter, d.ocnt, d.omin,
+                    d.omax, d.osum, d.oavg, d.oflags);
+            }
         }
         CHK(op, hipEventRecord(slot_ev, cs));
         op->free_slots.push_back({c.slot, slot_ev});
         pend.push_back({slab, ev});
     }
     /* phase 2: sorts + column D2H + job hand-off */
-    for (size_t ci = g0; ci < g1c; ci++) {
-        auto& c = closed[ci];
-        int slab = pend[ci - g0].slab;
-        hipEvent_t ev = pend[ci - g0].ev;
+    for (int i = 0; i < *g1c; i++) {
+        const Closed& c = cl[i];
+        int slab = pend[i].slab;
+        hipEvent_t ev = pend[i].ev;
         dz_window_op::DevEmit& d = op->e_dev[slab];
-        const bool dev_path = op->n_keys > 65536;
-        int csi = (int)((ci - g0) % dz_window_op::E_CSTREAMS);
+        int csi = i % dz_window_op::E_CSTREAMS;
         hipStream_t cs = op->c_streams[csi];
         if (dev_path && op->n_keys > 0) {
             /* adaptive: when the last close passed few groups (filtered
@@ -1890,22 +1703,97 @@ static dz_status trigger_windows(dz_window_op* op) {
         CHK(op, hipEventRecord(ev, cs));
         {
             std::lock_guard<std::mutex> lk(op->e_mtx);
-            dz_window_op::EmitJob j;
-            j.ev = ev;
+            dz_window_op::EmitJob j = make_job(op, c, ev);
             j.slab = slab;
-            j.wstart = c.start;
-            j.wend = c.end;
-            j.n_keys = op->n_keys;
-            j.kcap = op->kcap;
-            j.ticket = op->e_ticket_next++;
             j.device = dev_path;
             j.cs = csi;
             op->e_jobs.push_back(std::move(j));
         }
     }
     op->e_cv.notify_all(); /* one wakeup per group, not per close */
-    g0 = g1c;
-    } /* group loop */
+    return DZ_OK;
+}
+
+/* trigger_windows (grouped_window_agg_stream.rs:220-253): closed windows are
+ * copied D2H asynchronously and built by the worker thread off the push
+ * critical path; dz_window_op_drain/finish wait for completion. */
+static dz_status trigger_windows(dz_window_op* op) {
+    if (!op->has_wm) return DZ_OK;
+    std::vector<Closed> closed;
+    for (auto it = op->open.begin(); it != op->open.end();) {
+        if (op->watermark >= it->second.end) {
+            closed.push_back({it->first, it->second.end, it->second.slot,
+                              it->second.row_base});
+            it = op->open.erase(it);
+        } else {
+            ++it;
+        }
+    }
+    if (closed.empty()) return DZ_OK;
+    if (ensure_emission(op) != DZ_OK) return DZ_ERR;
+    HostTimer ht(op, "h_emit_enqueue");
+    /* emission kernels run on the copy stream AFTER the compute stream's
+     * folds for these slots */
+    hipEvent_t evA;
+    {
+        std::lock_guard<std::mutex> lk(op->e_mtx);
+        evA = take_event(op);
+    }
+    {
+        HostTimer htf(op, "h_trig_fence");
+        CHK(op, hipEventRecord(evA, op->stream));
+        for (int s = 0; s < dz_window_op::E_CSTREAMS; s++)
+            CHK(op, hipStreamWaitEvent(op->c_streams[s], evA, 0));
+    }
+    {
+        std::lock_guard<std::mutex> lk(op->e_mtx);
+        op->e_ev_pool.push_back(evA);
+    }
+    /* Closes are enqueued in GROUPS bounded by half the slab pool: the
+     * per-close strategy's phase 1 must never wait for slabs whose release
+     * depends on the same group's phase 2 (deadlock). */
+    constexpr size_t EGROUP = dz_window_op::E_POOL / 2;
+    /* variance-declaring ops take the host-built path at every key count
+     * (the device chains carry no m2 column) */
+    const bool dev_path_g = op->n_keys > 65536 && !op->has_var;
+    /* small closes (passer hint at or below the threshold) share one
+     * group-batched device chain; large ones keep the per-close chain */
+    static const uint32_t group_max = [] {
+        const char* v = getenv("DZ_EMIT_GROUP_MAX");
+        return v ? (uint32_t)atoi(v) : 65536u;
+    }();
+    const bool grouped_ok = dev_path_g && op->kcap > 0 &&
+        op->kcap <= dz_window_op::E_GELEMS &&
+        op->e_nt_hint.load(std::memory_order_relaxed) <= group_max &&
+        op->batch_seq < (1u << 19);
+    size_t g0 = 0;
+    while (g0 < closed.size()) {
+        size_t gstep = EGROUP;
+        if (op->has_var)
+            gstep = std::min<size_t>(gstep,
+                                     (size_t)std::max(1, op->e_gbuf_closes));
+        if (grouped_ok)
+            gstep = std::min<size_t>(gstep, std::max<size_t>(1,
+                (size_t)(dz_window_op::E_GELEMS / op->kcap)));
+        const Closed* cl = closed.data() + g0;
+        int g1c = (int)(std::min(closed.size(), g0 + gstep) - g0);
+        dz_status st;
+        if (grouped_ok) {
+            st = enqueue_group_device(op, cl, g1c);
+        } else if (!dev_path_g && op->e_gbufs[0]) {
+            st = enqueue_group_host(op, cl, g1c);
+        } else if (op->has_var) {
+            /* unreachable while ensure_emission holds: the per-close staging
+             * carries no m2 column — refuse rather than emit without it */
+            op->err = "internal: variance aggregates need the pinned group "
+                      "buffers (allocation missing)";
+            st = DZ_ERR;
+        } else {
+            st = enqueue_per_close(op, cl, g1c, &g1c);
+        }
+        if (st != DZ_OK) return DZ_ERR;
+        g0 += (size_t)g1c;
+    }
     return DZ_OK;
 }
 
@@ -2739,28 +2627,18 @@ extern "C" dz_status dz_window_op_poll(dz_window_op* op, const dz_out_batch** ou
          * views into the pinned packed span the OutBuf holds; group-span
          * slices carry their offset in packed_off (whole-slab batches have
          * packed_off 0) */
-        const char* p = ob.packed;
-        const size_t ntp = ob.packed_nt;
-        const size_t po = ob.packed_off;
-        for (size_t a = 0; a < op->aggs.size(); a++) {
-            const void* ptr = nullptr;
-            switch (op->aggs[a].op) {
-                case DZ_AGG_COUNT: ptr = p + ntp * 8 + po * 8; break;
-                case DZ_AGG_MIN: ptr = p + ntp * 16 + po * 8; break;
-                case DZ_AGG_MAX: ptr = p + ntp * 24 + po * 8; break;
-                case DZ_AGG_SUM: ptr = p + ntp * 32 + po * 8; break;
-                case DZ_AGG_AVG: ptr = p + ntp * 40 + po * 8; break;
-            }
-            ob.agg_ptrs.push_back(ptr);
-        }
+        const dz::PackedCols cols =
+            dz::packed_cols(ob.packed, ob.packed_nt, ob.packed_off);
+        for (size_t a = 0; a < op->aggs.size(); a++)
+            ob.agg_ptrs.push_back(packed_agg_col(cols, op->aggs[a].op));
         bool dense_key = !op->no_group && op->key_kind == DZ_KEY_DENSE_INT64;
-        ob.view.key_i64 = dense_key ? (const int64_t*)p + po
+        ob.view.key_i64 = dense_key ? cols.key
                                     : (ob.key_i64.empty() ? nullptr
                                                           : ob.key_i64.data());
         ob.view.key_offsets =
             ob.key_offsets.empty() ? nullptr : ob.key_offsets.data();
         ob.view.key_data = ob.key_data.empty() ? nullptr : ob.key_data.data();
-        ob.view.agg_valid = (const uint8_t*)(p + ntp * 52 + po);
+        ob.view.agg_valid = cols.flags;
     } else {
         for (size_t a = 0; a < op->aggs.size(); a++) {
             if (op->aggs[a].op == DZ_AGG_COUNT)
@@ -2872,10 +2750,17 @@ extern "C" dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
         op->err = "filter agg index out of range";
         return DZ_ERR;
     }
-    op->has_filter = true;
     op->f_idx = agg_idx;
-    op->f_cmp = cmp;
-    op->f_lit = literal;
+    op->filter.on = 1;
+    op->filter.cmp = cmp;
+    op->filter.lit = literal;
+    switch (op->aggs[agg_idx].op) {
+        case DZ_AGG_COUNT: op->filter.field = 0; break;
+        case DZ_AGG_MIN: op->filter.field = 1; break;
+        case DZ_AGG_MAX: op->filter.field = 2; break;
+        case DZ_AGG_SUM: op->filter.field = 3; break;
+        default: op->filter.field = 4; break;
+    }
     return DZ_OK;
 }
 
