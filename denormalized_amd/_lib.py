@@ -172,6 +172,10 @@ def lib():
                 ctypes.POINTER(ctypes.c_double)]
         except AttributeError:  # older engine build (A/B hook)
             pass
+        try:
+            L.dz_debug_intern_fp_bits.argtypes = [p, ctypes.c_int32]
+        except AttributeError:  # older engine build (A/B hook)
+            pass
         L.dz_version.restype = ctypes.c_char_p
         _lib = L
     return _lib
@@ -283,6 +287,12 @@ class WindowOp:
         self._check(self._L.dz_window_op_push_device_utf8(
             self._h, n, d_ts, d_key_offsets, d_key_data, d_vals),
             "push_device_utf8")
+
+    def debug_intern_fp_bits(self, bits):
+        """Test hook: mask intern fingerprints to `bits` bits (forces
+        collisions). Only before the first push_device_utf8."""
+        self._check(self._L.dz_debug_intern_fp_bits(self._h, bits),
+                    "debug_intern_fp_bits")
 
     def poll(self, copy=True):
         """Returns a dict of numpy arrays for one emitted batch, or None.

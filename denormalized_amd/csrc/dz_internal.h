@@ -54,10 +54,14 @@ void launch_gen(hipStream_t stream, uint64_t seed, int64_t t0, int64_t start_row
 
 /* device utf8 intern (GroupValues::intern analog at device rate) */
 void launch_intern(hipStream_t stream, const int32_t* d_offs, const char* d_data,
-                   int64_t n, uint4* tab /* {fp, id, len|off<<6} slots */,
+                   int64_t n,
+                   uint4* tab /* 32 B slots {fp, id, lenoff | inline[16]} */,
                    uint32_t* tab_row, uint32_t p_mask, uint32_t* id_off,
-                   uint32_t* id_len, char* pool, uint32_t* ctrs,
+                   uint32_t* id_len, char* pool,
+                   uint32_t* ctrs /* next id, pool cursor, fresh-batch seq */,
                    uint32_t id_cap, uint32_t pool_cap, int32_t* out_kid,
+                   uint32_t seq /* this batch's number, never 0 */,
+                   uint64_t fp_mask /* all-ones outside collision tests */,
                    uint32_t* d_dbg);
 
 /* synthetic utf8 key generator ("sensor_{k}"): lens pass and/or fill pass */

@@ -137,10 +137,17 @@ __device__ __forceinline__ bool bytes_eq(const char* a, const char* b,
     return true;
 }
 
-/* table slot: 16 B {fp lo, fp hi, id, len|off<<6} — ONE load serves the
- * probe AND the steady-state resolve (separate fp/id arrays cost a second
- * dependent access per row). lenoff packs len<=63 and pool off<2^26;
- * larger keys resolve through the id_off/id_len fallback arrays. */
+/* table slot: 32 B, 32 B-aligned (never straddles a 128 B line), two uint4s:
+ *   [0] {fp lo, fp hi, id, lenoff}   [1] inline[16] (key bytes, zero-padded)
+ * fp is the 8 B word the claim CAS works on; everything else is written by
+ * k_intern_assign only. ONE cache line serves the probe, the resolve AND
+ * the byte-verify of keys up to 16 B (the pool gather they replace was ~11
+ * fully divergent byte loads per row). lenoff low 6 bits:
+ *   0..62  key length, pool offset (< 2^26) in the upper 26 bits
+ *   63     upper bits 0..16: the key's length, its bytes are in inline[]
+ *          upper bits all-ones: resolve through the id_off/id_len arrays */
+constexpr uint32_t INTERN_INLINE_MAX = 16;
+
 __device__ __forceinline__ uint64_t slot_fp(const uint4& v) {
     return (uint64_t)v.x | ((uint64_t)v.y << 32);
 }
@@ -148,62 +155,112 @@ __device__ __forceinline__ uint64_t slot_fp(const uint4& v) {
 __global__ __launch_bounds__(BLOCK) void k_intern_claim(const int32_t* offs,
         const char* data, int64_t n, uint4* tab, uint32_t* tab_row,
         const uint32_t* id_off, const uint32_t* id_len,
-        const char* pool, uint32_t p_mask, int32_t* out_kid, uint32_t* dbg) {
+        const char* pool, uint32_t p_mask, uint64_t fp_mask, int32_t* out_kid,
+        uint32_t* fresh_seq, uint32_t seq, uint32_t* dbg) {
     /* phase 1: every row probes; exactly one row CASes each new
      * fingerprint in, recording itself as the claiming row. No lane ever
      * waits on another (a publish-wait design can cycle across waves).
      * STEADY STATE (slot already has an assigned id from an earlier batch):
-     * byte-verify and resolve right here — out_kid = ~id — so the lookup
-     * phase touches key bytes only for rows of freshly claimed keys. */
+     * byte-verify and resolve right here — out_kid = id, final. Rows of
+     * keys claimed in THIS batch store ~slot (negative) for the lookup
+     * phase and stamp *fresh_seq with this batch's sequence number; assign
+     * and lookup return at once when the stamp is not theirs. */
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += stride) {
         const int32_t o0 = offs[i];
         const int32_t len = offs[i + 1] - o0;
-        uint64_t fp = fnv1a64(data + o0, len);
+        const char* p = data + o0;
+        /* short keys: keep the bytes read for the hash in two registers
+         * (lo = bytes 0..7, hi = bytes 8..15) for the inline verify */
+        uint64_t klo = 0, khi = 0, fp;
+        if ((uint32_t)len <= INTERN_INLINE_MAX) {
+            fp = 1469598103934665603ULL;
+            const int32_t n0 = len < 8 ? len : 8;
+            for (int32_t j = 0; j < n0; j++) {
+                const uint64_t b = (uint8_t)p[j];
+                fp = (fp ^ b) * 1099511628211ULL;
+                klo |= b << (8 * j);
+            }
+            for (int32_t j = 8; j < len; j++) {
+                const uint64_t b = (uint8_t)p[j];
+                fp = (fp ^ b) * 1099511628211ULL;
+                khi |= b << (8 * (j - 8));
+            }
+        } else {
+            fp = fnv1a64(p, len);
+        }
+        fp &= fp_mask; /* all-ones outside the collision tests */
         if (!fp) fp = 1; /* 0 marks an empty slot */
         uint32_t slot = (uint32_t)fp & p_mask;
         int32_t out;
         for (uint32_t probes = 0;; slot = (slot + 1) & p_mask) {
-            /* fp first as an aligned 8 B load (single-copy atomic vs a
-             * concurrent claim CAS — the fp halves of a 16 B vector load
-             * are not guaranteed tear-free); the id/lenoff follow-up hits
-             * the SAME cache line, so the steady state still pays one
-             * memory-system access */
-            uint64_t got = ((const uint64_t*)tab)[(size_t)slot * 2];
-            if (got == 0) {
-                got = (uint64_t)atomicCAS(
-                    (unsigned long long*)&tab[slot], 0ULL,
-                    (unsigned long long)fp);
-                if (got == 0) {
-                    tab_row[slot] = (uint32_t)i; /* claimed: I define bytes */
-                    out = (int32_t)slot;
-                    break;
-                }
+            /* both halves of the slot, issued together: one line. A slot
+             * whose id is assigned was written whole by an earlier kernel,
+             * so none of its words can tear and this load is all the
+             * steady state needs. */
+            const uint4 a = tab[(size_t)slot * 2];
+            const uint4 b = tab[(size_t)slot * 2 + 1];
+            const uint32_t cand = a.z;
+            const uint32_t lo = a.w;
+            const bool assigned = cand != ~0u;
+            const bool fpeq = slot_fp(a) == fp;
+            /* the whole short-key verdict as ONE predicate (non-short-
+             * circuit on purpose: both loads are then needed before the
+             * first branch and stay two back-to-back 16 B loads) */
+            const uint64_t slo = (uint64_t)b.x | ((uint64_t)b.y << 32);
+            const uint64_t shi = (uint64_t)b.z | ((uint64_t)b.w << 32);
+            const bool inline_hit = assigned & fpeq &
+                ((uint32_t)len <= INTERN_INLINE_MAX) &
+                (lo == (((uint32_t)len << 6) | 63u)) & (slo == klo) &
+                (shi == khi);
+            if (inline_hit) {
+                out = (int32_t)cand;
+                break;
             }
-            if (got == fp) { /* same key (fp64 exact) */
-                const uint4 v = tab[slot]; /* L1-hot: same line as the fp */
-                const uint32_t cand = v.z;
-                if (cand != ~0u) {
-                    const uint32_t lo = v.w;
-                    const uint32_t clen = lo & 63u;
+            if (assigned) {
+                const uint32_t clen = lo & 63u;
+                const bool is_inline =
+                    clen == 63u && (lo >> 6) <= INTERN_INLINE_MAX;
+                if (fpeq && !is_inline) { /* same key unless fp64 collides */
                     const bool fits = clen != 63u;
                     const uint32_t co = fits ? (lo >> 6) : id_off[cand];
                     const uint32_t cl = fits ? clen : id_len[cand];
-                    if (cl == (uint32_t)len &&
-                        bytes_eq(pool + co, data + o0, len)) {
-                        out = ~(int32_t)cand; /* resolved inline */
+                    if (cl == (uint32_t)len && bytes_eq(pool + co, p, len)) {
+                        out = (int32_t)cand;
                         break;
                     }
-                    /* fp64 collision with a different key: probe on */
-                } else {
-                    out = (int32_t)slot; /* fresh this batch: lookup decides */
+                }
+                /* a different key (fp64 collision or another home slot's
+                 * overflow): probe on */
+            } else {
+                /* empty, or claimed in this batch (assign runs after this
+                 * kernel, so an unassigned id stays unassigned throughout):
+                 * fp again as an aligned 8 B ATOMIC load (single-copy atomic
+                 * vs a concurrent claim CAS — the fp halves of the 16 B
+                 * vector load above are not guaranteed tear-free, and a
+                 * plain reload could legally be folded into it), then the
+                 * CAS */
+                uint64_t got = __hip_atomic_load(
+                    (const uint64_t*)tab + (size_t)slot * 4, __ATOMIC_RELAXED,
+                    __HIP_MEMORY_SCOPE_AGENT);
+                if (got == 0)
+                    got = (uint64_t)atomicCAS(
+                        (unsigned long long*)&tab[(size_t)slot * 2], 0ULL,
+                        (unsigned long long)fp);
+                if (got == 0 || got == fp) {
+                    /* got == 0: claimed, I define the bytes; got == fp:
+                     * fresh this batch, lookup decides */
+                    if (got == 0) tab_row[slot] = (uint32_t)i;
+                    *fresh_seq = seq;
+                    out = ~(int32_t)slot;
                     break;
                 }
             }
             if (++probes > p_mask) {
                 dbg[3] = 4; /* table full */
-                out = (int32_t)slot;
+                *fresh_seq = seq;
+                out = ~(int32_t)slot;
                 break;
             }
         }
@@ -215,14 +272,18 @@ __global__ __launch_bounds__(BLOCK) void k_intern_assign(uint4* tab,
         uint32_t* tab_row, uint32_t p_count,
         const int32_t* offs, const char* data, uint32_t* id_off,
         uint32_t* id_len, char* pool, uint32_t* ctrs, uint32_t id_cap,
-        uint32_t pool_cap, uint32_t* dbg) {
+        uint32_t pool_cap, const uint32_t* fresh_seq, uint32_t seq,
+        uint32_t* dbg) {
     /* phase 2 (after claim completes, stream-ordered): one thread per slot;
-     * slots claimed this batch (fp set, id still unassigned) get a dense id
-     * and their first-seen bytes copied into the persistent pool. */
+     * slots claimed this batch (fp set, id still unassigned) get a dense id,
+     * their first-seen bytes copied into the persistent pool and — up to
+     * 16 B — into the slot itself. The only writer of everything but fp; no
+     * reader runs concurrently, so no slot is ever seen half-written. */
+    if (*fresh_seq != seq) return; /* nothing was claimed in this batch */
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t sl = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
          sl < p_count; sl += stride) {
-        uint4 v = tab[sl];
+        uint4 v = tab[(size_t)sl * 2];
         if (slot_fp(v) == 0 || v.z != ~0u) continue;
         const uint32_t r = tab_row[sl];
         const int32_t o0 = offs[r];
@@ -233,37 +294,49 @@ __global__ __launch_bounds__(BLOCK) void k_intern_assign(uint4* tab,
             dbg[3] = nid >= id_cap ? 1 : 2; /* capacity guard */
             continue;
         }
-        for (int32_t j = 0; j < len; j++) pool[po + j] = data[o0 + j];
+        uint64_t klo = 0, khi = 0;
+        for (int32_t j = 0; j < len; j++) {
+            const uint8_t c = (uint8_t)data[o0 + j];
+            pool[po + j] = (char)c;
+            if (j < 8) klo |= (uint64_t)c << (8 * j);
+            else if (j < (int32_t)INTERN_INLINE_MAX)
+                khi |= (uint64_t)c << (8 * (j - 8));
+        }
         id_off[nid] = po;
         id_len[nid] = (uint32_t)len;
         v.z = nid;
-        /* lenoff fast path: len<=62 and off<2^26 (63 in the len field =
-         * "use the fallback arrays") */
-        v.w = (len <= 62 && po < (1u << 26)) ? ((po << 6) | (uint32_t)len)
-                                             : 0xFFFFFFFFu; /* len field 63
-                                                => use the fallback arrays */
-        tab[sl] = v;
+        /* lenoff (slot comment above): inline up to 16 B, pool offset fast
+         * path for len<=62 and off<2^26, else the fallback arrays */
+        if ((uint32_t)len <= INTERN_INLINE_MAX) {
+            v.w = ((uint32_t)len << 6) | 63u;
+            tab[(size_t)sl * 2 + 1] = make_uint4((uint32_t)klo,
+                (uint32_t)(klo >> 32), (uint32_t)khi, (uint32_t)(khi >> 32));
+        } else {
+            v.w = (len <= 62 && po < (1u << 26)) ? ((po << 6) | (uint32_t)len)
+                                                 : 0xFFFFFFFFu;
+        }
+        tab[(size_t)sl * 2] = v;
     }
 }
 
 __global__ __launch_bounds__(BLOCK) void k_intern_lookup(const int32_t* offs,
         const char* data, int64_t n, const uint4* tab,
         const uint32_t* id_off, const uint32_t* id_len, const char* pool,
-        int32_t* out_kid, uint32_t* dbg) {
-    /* phase 3 (after assign): resolve each row's slot (stashed by the claim
-     * phase) to its dense id, byte-verifying against the pool — distinct
-     * keys sharing a full 64-bit fingerprint cannot be interned and are
-     * FLAGGED (results then fail loudly via the guard cells). */
+        int32_t* out_kid, const uint32_t* fresh_seq, uint32_t seq,
+        uint32_t* dbg) {
+    /* phase 3 (after assign): resolve each row's slot (stashed as ~slot by
+     * the claim phase) to its dense id, byte-verifying against the pool —
+     * distinct keys sharing a full 64-bit fingerprint cannot be interned
+     * and are FLAGGED (results then fail loudly via the guard cells). In
+     * steady state no row is stashed and the whole pass is skipped. */
+    if (*fresh_seq != seq) return; /* claim resolved every row */
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += stride) {
         const int32_t v = out_kid[i];
-        if (v < 0) { /* resolved inline by the claim phase */
-            out_kid[i] = ~v;
-            continue;
-        }
-        const uint32_t slot = (uint32_t)v;
-        const uint32_t cand = tab[slot].z;
+        if (v >= 0) continue; /* resolved by the claim phase: final */
+        const uint32_t slot = (uint32_t)~v;
+        const uint32_t cand = tab[(size_t)slot * 2].z;
         int32_t id = 0;
         if (cand == ~0u) {
             dbg[3] = 5; /* capacity overflow left the slot unassigned */
@@ -283,20 +356,23 @@ void launch_intern(hipStream_t s, const int32_t* d_offs, const char* d_data,
                    int64_t n, uint4* tab, uint32_t* tab_row, uint32_t p_mask,
                    uint32_t* id_off, uint32_t* id_len, char* pool,
                    uint32_t* ctrs, uint32_t id_cap, uint32_t pool_cap,
-                   int32_t* out_kid, uint32_t* dbg) {
+                   int32_t* out_kid, uint32_t seq, uint64_t fp_mask,
+                   uint32_t* dbg) {
     int blocks = (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048);
     if (blocks < 1) blocks = 1;
     const uint32_t P = p_mask + 1;
     int sblocks = (int)std::min<uint32_t>((P + BLOCK - 1) / BLOCK, 2048);
+    uint32_t* fresh_seq = ctrs + 2;
     hipLaunchKernelGGL(k_intern_claim, dim3(blocks), dim3(BLOCK), 0, s, d_offs,
                        d_data, n, tab, tab_row, id_off, id_len,
-                       pool, p_mask, out_kid, dbg);
+                       pool, p_mask, fp_mask, out_kid, fresh_seq, seq, dbg);
     hipLaunchKernelGGL(k_intern_assign, dim3(sblocks), dim3(BLOCK), 0, s,
                        tab, tab_row, P, d_offs, d_data, id_off,
-                       id_len, pool, ctrs, id_cap, pool_cap, dbg);
+                       id_len, pool, ctrs, id_cap, pool_cap, fresh_seq, seq,
+                       dbg);
     hipLaunchKernelGGL(k_intern_lookup, dim3(blocks), dim3(BLOCK), 0, s,
                        d_offs, d_data, n, tab, id_off,
-                       id_len, pool, out_kid, dbg);
+                       id_len, pool, out_kid, fresh_seq, seq, dbg);
 }
 
 /* synthetic utf8 key generator: "sensor_{k}" with k from the SAME splitmix

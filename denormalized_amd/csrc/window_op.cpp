@@ -280,13 +280,17 @@ struct dz_window_op {
 
     /* device utf8 intern (GroupValues::intern at device rate). Fixed-capacity
      * from n_keys_hint at create; capacity overflow flags d_dbg[3]. */
-    uint4* d_itab = nullptr;        /* 16 B slots {fp, id, len|off<<6} */
+    uint4* d_itab = nullptr;        /* 32 B slots: {fp, id, lenoff} then the
+                                     * key's bytes inline when len <= 16 */
     uint32_t* d_itab_row = nullptr; /* claiming row, valid within one claim */
     uint32_t i_pmask = 0;
     uint32_t* d_ioff = nullptr;     /* per-id {pool offset, byte length} */
     uint32_t* d_ilen = nullptr;
     char* d_ipool = nullptr;        /* first-seen key bytes */
-    uint32_t* d_ictrs = nullptr;    /* [0]=next id, [1]=pool cursor */
+    uint32_t* d_ictrs = nullptr;    /* [0]=next id, [1]=pool cursor, [2]=seq
+                                     * of the last batch that claimed keys */
+    uint32_t i_seq = 0;             /* intern batch sequence number */
+    uint64_t i_fpmask = ~0ULL;      /* dz_debug_intern_fp_bits */
     uint32_t i_idcap = 0, i_poolcap = 0;
     int32_t* d_ikid[2] = {};        /* interned dense ids, per pipeline buf */
     int64_t i_kid_cap[2] = {0, 0};
@@ -2322,18 +2326,19 @@ static dz_status ensure_intern(dz_window_op* op, int64_t n) {
         op->i_idcap = P / 2;
         op->i_poolcap = (uint32_t)std::min<uint64_t>((uint64_t)op->i_idcap * 64,
                                                      1u << 31);
-        CHK(op, hipMalloc(&op->d_itab, (size_t)P * 16));
+        CHK(op, hipMalloc(&op->d_itab, (size_t)P * 32));
         CHK(op, hipMalloc(&op->d_itab_row, (size_t)P * 4));
         CHK(op, hipMalloc(&op->d_ioff, (size_t)op->i_idcap * 4));
         CHK(op, hipMalloc(&op->d_ilen, (size_t)op->i_idcap * 4));
         CHK(op, hipMalloc(&op->d_ipool, op->i_poolcap));
-        CHK(op, hipMalloc(&op->d_ictrs, 8));
-        /* fp halves zero (empty), id halves ~0 (unassigned): zero the whole
-         * table then set .z/.w lanes via a strided 0xFF fill */
-        CHK(op, hipMemsetAsync(op->d_itab, 0, (size_t)P * 16, op->stream));
-        CHK(op, hipMemset2DAsync((char*)op->d_itab + 8, 16, 0xFF, 8, P,
+        CHK(op, hipMalloc(&op->d_ictrs, 12));
+        /* fp zero (empty), id/lenoff ~0 (unassigned), inline bytes zero:
+         * zero the whole table then set the id/lenoff words via a strided
+         * 0xFF fill */
+        CHK(op, hipMemsetAsync(op->d_itab, 0, (size_t)P * 32, op->stream));
+        CHK(op, hipMemset2DAsync((char*)op->d_itab + 8, 32, 0xFF, 8, P,
                                  op->stream));
-        CHK(op, hipMemsetAsync(op->d_ictrs, 0, 8, op->stream));
+        CHK(op, hipMemsetAsync(op->d_ictrs, 0, 12, op->stream));
         /* the intern runs on i_stream: make the init visible there */
         CHK(op, hipStreamSynchronize(op->stream));
     }
@@ -2373,6 +2378,21 @@ static dz_status intern_sync_mirror(dz_window_op* op) {
     return DZ_OK;
 }
 
+extern "C" dz_status dz_debug_intern_fp_bits(dz_window_op* op, int32_t bits) {
+    if (!op) return DZ_ERR;
+    if (op->d_itab) {
+        op->err = "dz_debug_intern_fp_bits is legal only before the first "
+                  "device utf8 push";
+        return DZ_ERR;
+    }
+    if (bits < 1 || bits > 64) {
+        op->err = "dz_debug_intern_fp_bits: bits must be in 1..64";
+        return DZ_ERR;
+    }
+    op->i_fpmask = bits == 64 ? ~0ULL : ((1ULL << bits) - 1);
+    return DZ_OK;
+}
+
 extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
         int64_t n_rows, const int64_t* d_ts_ms, const int32_t* d_key_offsets,
         const char* d_key_data, const double* d_vals) {
@@ -2403,12 +2423,13 @@ extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
     int b = op->next_buf;
     if (op->consumed_valid[b])
         CHK(op, hipStreamWaitEvent(op->i_stream, op->ev_consumed[b], 0));
+    if (++op->i_seq == 0) op->i_seq = 1; /* 0 is the counter's initial value */
     timed_on(op, op->i_stream, "intern", (double)n_rows * 18, [&] {
         dz::launch_intern(op->i_stream, d_key_offsets, d_key_data, n_rows,
                           op->d_itab, op->d_itab_row,
                           op->i_pmask, op->d_ioff, op->d_ilen, op->d_ipool,
                           op->d_ictrs, op->i_idcap, op->i_poolcap,
-                          op->d_ikid[b], op->d_dbg);
+                          op->d_ikid[b], op->i_seq, op->i_fpmask, op->d_dbg);
     });
     if (stage_core(op, n_rows, d_ts_ms, op->d_ikid[b], d_vals, nullptr,
                    /*keys_are_dense=*/true, /*deferred=*/true,

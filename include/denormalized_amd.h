@@ -382,6 +382,15 @@ int64_t dz_debug_windows_for_range(int64_t min_ts, int64_t max_ts,
 int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count, double m2,
                               double* out);
 
+/* Test hook for the device utf8 intern: keep only the low `bits` (1..64)
+ * bits of every key fingerprint, so distinct keys collide on demand and the
+ * probe-on / byte-verify paths can be exercised. 64 (the default) masks
+ * nothing. Legal only before the operator's first device utf8 push; results
+ * are unaffected at any setting (verification stays byte-exact), except
+ * that two NEW colliding keys inside one batch fail at finish as documented
+ * for full 64-bit collisions. */
+dz_status dz_debug_intern_fp_bits(dz_window_op* op, int32_t bits);
+
 const char* dz_version(void);
 
 #ifdef __cplusplus
