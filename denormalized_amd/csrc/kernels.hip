@@ -1954,6 +1954,36 @@ __device__ __forceinline__ const char* j_ws(const char* p, const char* e) {
     return p;
 }
 
+__device__ __forceinline__ bool j_dig(char c) {
+    return (unsigned)(c - '0') <= 9u;
+}
+
+/* p is just past an opening quote: returns the closing quote's position, or
+ * e when the string is unterminated or holds a raw control byte (< 0x20,
+ * not JSON). Escape pairs are stepped over (their spelling is not
+ * validated); *esc reports that one was seen. */
+__device__ __forceinline__ const char* j_str(const char* p, const char* e,
+                                             bool* esc) {
+    while (p < e && *p != '"') {
+        if ((unsigned char)*p < 0x20) return e;
+        if (*p == '\\') {
+            *esc = true;
+            if (++p >= e) return e;
+        }
+        p++;
+    }
+    return p;
+}
+
+/* length of the literal w (n bytes) if it is spelled at p, else 0 */
+__device__ __forceinline__ int32_t j_lit(const char* p, const char* e,
+                                         const char* w, int32_t n) {
+    if (e - p < n) return 0;
+    for (int32_t i = 0; i < n; i++)
+        if (p[i] != w[i]) return 0;
+    return n;
+}
+
 __global__ __launch_bounds__(BLOCK) void k_json_parse(const char* buf,
         const int64_t* rec_off, const uint32_t* tot, int64_t nbytes,
         JsonFields jf, int64_t* o_ts, int64_t* o_kbeg, int32_t* o_klen,
@@ -1973,39 +2003,41 @@ __global__ __launch_bounds__(BLOCK) void k_json_parse(const char* buf,
         int32_t klen = 0;
         double val = 0.0;
         bool have_ts = false, have_key = false, have_val = false, bad = false;
+        bool subset = false; /* valid JSON outside the documented subset */
+        bool closed = false;
         p = j_ws(p, e);
         if (p >= e || *p != '{') bad = true;
-        if (!bad) p++;
-        while (!bad) {
+        if (!bad) {
+            p = j_ws(p + 1, e);
+            if (p < e && *p == '}') { p++; closed = true; } /* {} */
+        }
+        while (!bad && !closed) {
+            /* one member: "name" : value, then ',' (another member MUST
+             * follow) or the closing '}' */
             p = j_ws(p, e);
-            if (p < e && *p == '}') break;
-            if (p < e && *p == ',') { p++; continue; }
             if (p >= e || *p != '"') { bad = true; break; }
             const char* name = ++p;
-            while (p < e && *p != '"') {
-                if (*p == '\\') { bad = true; break; } /* escaped field names
-                                                        * unsupported */
-                p++;
-            }
-            if (bad || p >= e) { bad = true; break; }
+            bool nesc = false;
+            p = j_str(p, e, &nesc);
+            if (p >= e) { bad = true; break; }
             const int32_t nlen = (int32_t)(p - name);
             p++;
             p = j_ws(p, e);
             if (p >= e || *p != ':') { bad = true; break; }
             p = j_ws(p + 1, e);
             if (p >= e) { bad = true; break; }
+            /* names are matched on their raw bytes: a schema name spelled
+             * with escapes is not recognised (documented) */
             const bool is_ts = jf_eq(name, nlen, jf.ts_name, jf.ts_len);
             const bool is_key = jf_eq(name, nlen, jf.key_name, jf.key_len);
             const bool is_val = jf_eq(name, nlen, jf.val_name, jf.val_len);
             if (*p == '"') { /* string value */
                 const char* s = ++p;
-                while (p < e && *p != '"') {
-                    if (*p == '\\') { bad = true; break; } /* escapes: out of
-                                                            * the subset */
-                    p++;
-                }
-                if (bad || p >= e) { bad = true; break; }
+                bool esc = false;
+                p = j_str(p, e, &esc);
+                if (p >= e) { bad = true; break; }
                 if (is_key) {
+                    if (esc) { subset = bad = true; break; } /* escaped key */
                     kbeg = (int64_t)(s - buf);
                     klen = (int32_t)(p - s);
                     have_key = true;
@@ -2034,58 +2066,81 @@ __global__ __launch_bounds__(BLOCK) void k_json_parse(const char* buf,
                     p++;
                 }
                 if (depth != 0) { bad = true; break; }
-            } else { /* number / literal */
+            } else if (*p == 't' || *p == 'f' || *p == 'n') {
+                /* true / false / null, spelled exactly (what follows is
+                 * checked by the separator rule below) */
+                if (is_ts || is_key || is_val) { bad = true; break; }
+                const int32_t l = *p == 't' ? j_lit(p, e, "true", 4)
+                                : *p == 'f' ? j_lit(p, e, "false", 5)
+                                            : j_lit(p, e, "null", 4);
+                if (!l) { bad = true; break; }
+                p += l;
+            } else { /* number: -? (0 | [1-9][0-9]*) (. [0-9]+)? ([eE] [+-]? [0-9]+)? */
                 bool neg = false;
                 if (*p == '-') { neg = true; p++; }
-                if (p < e && (*p == 't' || *p == 'f' || *p == 'n')) {
-                    /* true/false/null: skip letters */
-                    if (is_ts || is_key || is_val) { bad = true; break; }
-                    while (p < e && *p >= 'a' && *p <= 'z') p++;
-                    continue;
-                }
+                if (p >= e || !j_dig(*p)) { bad = true; break; }
+                /* mant holds the first 19 SIGNIFICANT digits (zeros before
+                 * the first non-zero digit are not significant); nsig
+                 * saturates at 20, which is all the range checks need */
                 uint64_t mant = 0;
-                int32_t ndig = 0, frac = 0, exp10 = 0;
-                while (p < e && *p >= '0' && *p <= '9') {
-                    if (ndig < 19) mant = mant * 10 + (uint64_t)(*p - '0');
-                    ndig++;
+                int32_t nsig = 0, exp10 = 0;
+                int64_t frac = 0;
+                bool isint = true;
+                if (*p == '0') {
                     p++;
+                    if (p < e && j_dig(*p)) { bad = true; break; } /* 01 */
+                } else {
+                    while (p < e && j_dig(*p)) {
+                        if (nsig < 19) mant = mant * 10 + (uint64_t)(*p - '0');
+                        nsig += nsig < 20;
+                        p++;
+                    }
                 }
                 if (p < e && *p == '.') {
+                    isint = false;
                     p++;
-                    while (p < e && *p >= '0' && *p <= '9') {
-                        if (ndig < 19) {
-                            mant = mant * 10 + (uint64_t)(*p - '0');
-                            ndig++;
-                            frac++;
-                        } else {
-                            ndig++;
+                    if (p >= e || !j_dig(*p)) { bad = true; break; } /* 1. */
+                    while (p < e && j_dig(*p)) {
+                        if (nsig > 0 || *p != '0') {
+                            if (nsig < 19)
+                                mant = mant * 10 + (uint64_t)(*p - '0');
+                            nsig += nsig < 20;
                         }
+                        frac++;
                         p++;
                     }
                 }
                 if (p < e && (*p == 'e' || *p == 'E')) {
+                    isint = false;
                     p++;
                     bool eneg = false;
                     if (p < e && (*p == '+' || *p == '-')) {
                         eneg = *p == '-';
                         p++;
                     }
-                    int32_t ev = 0;
-                    while (p < e && *p >= '0' && *p <= '9') {
-                        ev = ev * 10 + (*p - '0');
+                    if (p >= e || !j_dig(*p)) { bad = true; break; } /* 1e */
+                    int32_t ev = 0; /* saturates far outside +-22 */
+                    while (p < e && j_dig(*p)) {
+                        if (ev < 100000) ev = ev * 10 + (*p - '0');
                         p++;
                     }
                     exp10 = eneg ? -ev : ev;
                 }
+                if (is_key) { bad = true; break; } /* wrong type */
                 if (is_ts) {
-                    if (frac || exp10) { bad = true; break; }
-                    ts = neg ? -(int64_t)mant : (int64_t)mant;
+                    /* an integer literal within int64; 19 digits cannot
+                     * wrap the u64 mantissa */
+                    const uint64_t lim = neg ? (1ULL << 63) : (1ULL << 63) - 1;
+                    if (!isint || nsig > 19 || mant > lim) {
+                        subset = bad = true;
+                        break;
+                    }
+                    ts = (int64_t)(neg ? 0 - mant : mant);
                     have_ts = true;
                 } else if (is_val) {
-                    const int32_t e10 = exp10 - frac;
-                    if (ndig > 15 || e10 > 22 || e10 < -22) {
-                        dbg[2] = 2; /* outside the exact fast path */
-                        bad = true;
+                    const int64_t e10 = (int64_t)exp10 - frac;
+                    if (nsig > 15 || e10 > 22 || e10 < -22) {
+                        subset = bad = true; /* outside the exact fast path */
                         break;
                     }
                     double d = (double)mant;
@@ -2094,9 +2149,16 @@ __global__ __launch_bounds__(BLOCK) void k_json_parse(const char* buf,
                     have_val = true;
                 }
             }
+            p = j_ws(p, e);
+            if (p < e && *p == ',') { p++; continue; }
+            if (p < e && *p == '}') { p++; closed = true; break; }
+            bad = true;
         }
+        /* only space / tab / CR may follow the closing brace */
+        if (!bad && j_ws(p, e) != e) bad = true;
         if (bad || !have_ts || !have_key || !have_val) {
-            dbg[2] = bad ? 1 : 3; /* malformed / missing schema field */
+            /* 2: outside the subset, 1: malformed, 3: missing schema field */
+            dbg[2] = subset ? 2 : (bad ? 1 : 3);
             ts = 0; kbeg = rec_off[r]; klen = 0; val = 0.0;
         }
         o_ts[r] = ts;

@@ -3122,8 +3122,10 @@ extern "C" int64_t dz_join_op_unmatched(dz_join_op* op) {
 /* Newline-delimited records -> (ts int64, utf8 key column, f64 value) */
 /* device columns shaped for dz_window_op_push_device_utf8. Documented */
 /* subset (flagged loudly otherwise): no escape sequences inside the   */
-/* schema fields' strings/names, numeric literals within the exact     */
-/* Clinger fast path (<=15 significant digits, |decimal exp| <= 22).   */
+/* schema fields' names or the key string, values within the exact     */
+/* Clinger fast path (<=15 significant digits, |decimal exp| <= 22),   */
+/* timestamps int64 integer literals; strict JSON structure otherwise  */
+/* (include/denormalized_amd.h has the full wording).                  */
 /* ------------------------------------------------------------------ */
 
 struct dz_json_decoder {
@@ -3145,7 +3147,7 @@ struct dz_json_decoder {
     double* o_val[2] = {};
     int32_t* o_koff[2] = {};
     char* o_kdata[2] = {};
-    int64_t rec_cap = 0, kdata_cap = 0;
+    int64_t rec_cap[2] = {}, kdata_cap[2] = {}; /* per buffer: see growth */
     int cur = 0;
     int64_t n_rec = 0;
 };
@@ -3224,6 +3226,9 @@ extern "C" dz_status dz_json_decode(dz_json_decoder* d, const char* d_bytes,
     DCHK(d, hipSetDevice(d->device));
     d->n_rec = 0;
     if (n_bytes <= 0) return DZ_OK;
+    /* the guard cells report THIS decode only: a rejected batch must not
+     * poison the handle (stream-ordered ahead of the parse) */
+    DCHK(d, hipMemsetAsync(d->d_dbg, 0, 16, d->stream));
     int C = (int)std::min<int64_t>(512,
                                    std::max<int64_t>(1, (n_bytes + 8191) / 8192));
     int64_t chunk = (n_bytes + C - 1) / C;
@@ -3238,26 +3243,35 @@ extern "C" dz_status dz_json_decode(dz_json_decoder* d, const char* d_bytes,
     DCHK(d, hipStreamSynchronize(d->stream));
     const int64_t nrec = d->h_tot[0];
     if (nrec == 0) return DZ_OK;
-    if (nrec > d->rec_cap || n_bytes > d->kdata_cap) {
-        /* growth frees columns a downstream window op may still read
-         * under the borrowed-push contract: full-device barrier first */
+    const int b = d->cur ^ 1;
+    if (nrec > d->rec_cap[b] || n_bytes > d->kdata_cap[b]) {
+        /* Growth regrows ONLY the buffer this decode writes. The other one
+         * holds the last decode's columns, which a downstream window op
+         * still reads at its next push (borrowed-push contract): freeing
+         * them here handed it dangling pointers whenever a batch was a few
+         * bytes larger than every one before. The regrown buffer held the
+         * decode before last, whose consumer kernels may still be in
+         * flight on other streams: full-device barrier first. */
         DCHK(d, hipDeviceSynchronize());
-        int64_t rc = std::max(nrec, d->rec_cap);
-        int64_t kc = std::max(n_bytes, d->kdata_cap);
-        for (int i = 0; i < 2; i++) {
-            hipFree(d->d_recoff[i]); hipFree(d->o_ts[i]); hipFree(d->o_kbeg[i]);
-            hipFree(d->o_klen[i]); hipFree(d->o_val[i]); hipFree(d->o_koff[i]);
-            hipFree(d->o_kdata[i]);
-            DCHK(d, hipMalloc(&d->d_recoff[i], (size_t)rc * 8));
-            DCHK(d, hipMalloc(&d->o_ts[i], (size_t)rc * 8));
-            DCHK(d, hipMalloc(&d->o_kbeg[i], (size_t)rc * 8));
-            DCHK(d, hipMalloc(&d->o_klen[i], (size_t)rc * 4));
-            DCHK(d, hipMalloc(&d->o_val[i], (size_t)rc * 8));
-            DCHK(d, hipMalloc(&d->o_koff[i], ((size_t)rc + 1) * 4));
-            DCHK(d, hipMalloc(&d->o_kdata[i], (size_t)kc));
-        }
-        d->rec_cap = rc;
-        d->kdata_cap = kc;
+        const int64_t rc = std::max(nrec, d->rec_cap[b]);
+        const int64_t kc = std::max(n_bytes, d->kdata_cap[b]);
+        hipFree(d->d_recoff[b]); hipFree(d->o_ts[b]); hipFree(d->o_kbeg[b]);
+        hipFree(d->o_klen[b]); hipFree(d->o_val[b]); hipFree(d->o_koff[b]);
+        hipFree(d->o_kdata[b]);
+        d->d_recoff[b] = d->o_ts[b] = d->o_kbeg[b] = nullptr;
+        d->o_klen[b] = d->o_koff[b] = nullptr;
+        d->o_val[b] = nullptr;
+        d->o_kdata[b] = nullptr;
+        d->rec_cap[b] = d->kdata_cap[b] = 0;
+        DCHK(d, hipMalloc(&d->d_recoff[b], (size_t)rc * 8));
+        DCHK(d, hipMalloc(&d->o_ts[b], (size_t)rc * 8));
+        DCHK(d, hipMalloc(&d->o_kbeg[b], (size_t)rc * 8));
+        DCHK(d, hipMalloc(&d->o_klen[b], (size_t)rc * 4));
+        DCHK(d, hipMalloc(&d->o_val[b], (size_t)rc * 8));
+        DCHK(d, hipMalloc(&d->o_koff[b], ((size_t)rc + 1) * 4));
+        DCHK(d, hipMalloc(&d->o_kdata[b], (size_t)kc));
+        d->rec_cap[b] = rc;
+        d->kdata_cap[b] = kc;
     }
     const int64_t nb = (nrec + 4095) / 4096;
     if (nb > d->bs_cap) {
@@ -3265,7 +3279,6 @@ extern "C" dz_status dz_json_decode(dz_json_decoder* d, const char* d_bytes,
         DCHK(d, hipMalloc(&d->d_blocksum, (size_t)nb * 4));
         d->bs_cap = nb;
     }
-    const int b = d->cur ^ 1;
     dz::launch_json_parse(d->stream, d_bytes, n_bytes, C, chunk, d->jf,
                           d->d_cnt + 512, d->d_cnt + 1024, d->d_recoff[b],
                           nrec, d->o_ts[b], d->o_kbeg[b], d->o_klen[b],
@@ -3276,8 +3289,10 @@ extern "C" dz_status dz_json_decode(dz_json_decoder* d, const char* d_bytes,
     DCHK(d, hipMemcpy(cells, d->d_dbg, 16, hipMemcpyDeviceToHost));
     if (cells[2]) {
         d->err = cells[2] == 2
-                     ? "numeric literal outside the exact parse subset "
-                       "(<=15 significant digits, |decimal exponent| <= 22)"
+                     ? "schema field outside the exact parse subset "
+                       "(value: <=15 significant digits, |decimal exponent| "
+                       "<= 22; timestamp: int64 integer literal; key: no "
+                       "escape sequences)"
                      : (cells[2] == 1 ? "malformed JSON record"
                                       : "record missing a schema field");
         return DZ_ERR;

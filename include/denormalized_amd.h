@@ -288,12 +288,33 @@ int64_t dz_join_op_unmatched(dz_join_op* op);
  * newline-delimited records, producing (int64 ts, utf8 key column, f64
  * value) device columns shaped for dz_window_op_push_device_utf8 — the
  * on-wire-bytes -> windowed-aggregate pipeline stays in HBM end to end.
- * Documented subset (anything else fails loudly): records are non-empty
- * '\n'-separated JSON objects; the three schema fields are top-level
- * (other fields, including nested objects/arrays, are skipped); no escape
- * sequences inside schema field names or the key string; numeric literals
- * within the exact Clinger fast path (<= 15 significant digits, |decimal
- * exponent| <= 22 — equal to strtod bit-for-bit there). */
+ * Input is strict JSON, as serde_json::from_slice takes it, one object per
+ * '\n'-separated line (a trailing '\n' opens no further record; a blank
+ * line is an error); inside that, a documented subset decodes and anything
+ * else fails loudly, with one message class per cause:
+ *  - "exact parse subset": valid JSON the exact parse does not cover.
+ *    VALUE: a JSON-grammar number with at most 15 significant digits and
+ *    |e10| <= 22, where the significant digits are the integer and fraction
+ *    digits as written minus the zeros before the first non-zero digit (on
+ *    either side of the point; trailing zeros count, an all-zero literal
+ *    has 1) and e10 = exponent - number of fraction digits, the exponent
+ *    evaluated without wraparound. There the result is (double)digits times
+ *    or divided by an exact power of ten: equal to strtod bit for bit.
+ *    TIMESTAMP: an integer literal (no fraction, no exponent) within int64;
+ *    -9223372036854775808 is INT64_MIN. KEY: a string whose raw bytes hold
+ *    no backslash; the empty key is legal.
+ *  - "malformed": not strict JSON (number grammar: no empty literal, "1.",
+ *    ".5", "1e", "01"; true/false/null spelled exactly; commas exactly
+ *    between members; no raw control byte in a string; only space, tab or
+ *    CR before '{' and after '}'), or a schema field of the wrong JSON type
+ *    (a string for a number, a number/null/nested value for the key).
+ *  - "missing": a schema field is absent.
+ * The three schema fields are top-level members matched on their raw name
+ * bytes (a schema name spelled with escapes is not recognised); when one is
+ * duplicated the last occurrence wins. Every other member is skipped and may
+ * be any JSON value under any name, escapes included. Not validated: the
+ * spelling of escape sequences, UTF-8, and the inside of a skipped nested
+ * object/array beyond matching its brackets and quotes. */
 
 typedef struct dz_json_decoder dz_json_decoder;
 
@@ -305,8 +326,11 @@ const char* dz_json_decoder_last_error(dz_json_decoder* d);
 
 /* Decode one device-resident byte buffer. Columns are retrieved with
  * dz_json_decoder_batch and stay valid until the SECOND-next decode
- * (double-buffered, covering a utf8 borrowed push across one step —
- * provided batch sizes do not grow, which reallocates). */
+ * (double-buffered, covering a utf8 borrowed push across one step; a
+ * larger batch regrows only the buffer it writes, so this holds across
+ * growth too). A rejected decode (DZ_ERR, message from
+ * dz_json_decoder_last_error) leaves n == 0, the last good batch's columns
+ * intact and the handle usable. n_bytes == 0 is DZ_OK with n == 0. */
 dz_status dz_json_decode(dz_json_decoder* d, const char* d_bytes,
                          int64_t n_bytes);
 dz_status dz_json_decoder_batch(dz_json_decoder* d, int64_t* n_out,
