@@ -18,6 +18,9 @@ constexpr int BLOCK = 256;          /* 4 waves */
 constexpr int WAVES_PER_BLOCK = BLOCK / 64;
 constexpr int MAX_RANGES = 4096;    /* window frames touched by one batch */
 constexpr int ST_RECORDS = 2048;    /* scatter staging records per supertile */
+/* intern claim: key bytes of one 256-row tile staged in LDS when their span
+ * is at most this (16 B/row average; the bench's 8-11 B keys span ~2.8 KB) */
+constexpr int INTERN_STAGE_BYTES = 4096;
 
 /* meta word packed per record: kloc (16b) | widx (12b) | valid (1b) */
 constexpr uint32_t META_KLOC_MASK = 0xFFFFu;

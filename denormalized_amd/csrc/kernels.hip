@@ -119,9 +119,12 @@ void launch_gen(hipStream_t s, uint64_t seed, int64_t t0, int64_t start_row,
 
 __device__ __forceinline__ uint64_t fnv1a64(const char* p, int32_t len) {
     /* byte-wise FNV-1a: measured FASTER than a word-at-a-time variant with
-     * unaligned dword loads on gfx950 (2.1 ms vs 0.68 ms per 8M-row batch
-     * for the whole intern chain) — short dependent byte chains schedule
-     * better than the split unaligned loads. */
+     * unaligned dword GLOBAL loads on gfx950 (2.1 ms vs 0.68 ms per 8M-row
+     * batch for the whole intern chain). The claim kernel no longer walks
+     * global memory here for short-span tiles: it stages a tile's key bytes
+     * in LDS and runs this chain against LDS (k_intern_claim). Reading the
+     * staged key as aligned dwords funnel-shifted into registers measured
+     * the same as the byte walk, so the byte walk stays. */
     uint64_t h = 1469598103934665603ULL;
     for (int32_t i = 0; i < len; i++) {
         h ^= (uint8_t)p[i];
@@ -152,6 +155,36 @@ __device__ __forceinline__ uint64_t slot_fp(const uint4& v) {
     return (uint64_t)v.x | ((uint64_t)v.y << 32);
 }
 
+/* fingerprint of one key + its first 16 bytes in two registers (lo = bytes
+ * 0..7, hi = bytes 8..15; zero for longer keys) for the inline verify. `p` is
+ * an LDS address on the staged path and a global one on the fallback path:
+ * force-inlined, each call site gets loads of its own address space. */
+__device__ __forceinline__ uint64_t key_fp_bytes(const uint8_t* p, int32_t len,
+                                                 uint64_t* klo, uint64_t* khi) {
+    uint64_t lo = 0, hi = 0, fp = 1469598103934665603ULL;
+    if ((uint32_t)len <= INTERN_INLINE_MAX) {
+        const int32_t n0 = len < 8 ? len : 8;
+        for (int32_t j = 0; j < n0; j++) {
+            const uint64_t b = p[j];
+            fp = (fp ^ b) * 1099511628211ULL;
+            lo |= b << (8 * j);
+        }
+        for (int32_t j = 8; j < len; j++) {
+            const uint64_t b = p[j];
+            fp = (fp ^ b) * 1099511628211ULL;
+            hi |= b << (8 * (j - 8));
+        }
+    } else {
+        fp = fnv1a64((const char*)p, len);
+    }
+    *klo = lo;
+    *khi = hi;
+    return fp;
+}
+
+/* stage granules: the span plus up to 15 B each of head and tail alignment */
+constexpr int INTERN_STAGE_GRAN = INTERN_STAGE_BYTES / 16 + 2;
+
 __global__ __launch_bounds__(BLOCK) void k_intern_claim(const int32_t* offs,
         const char* data, int64_t n, uint4* tab, uint32_t* tab_row,
         const uint32_t* id_off, const uint32_t* id_len,
@@ -164,32 +197,59 @@ __global__ __launch_bounds__(BLOCK) void k_intern_claim(const int32_t* offs,
      * byte-verify and resolve right here — out_kid = id, final. Rows of
      * keys claimed in THIS batch store ~slot (negative) for the lookup
      * phase and stamp *fresh_seq with this batch's sequence number; assign
-     * and lookup return at once when the stamp is not theirs. */
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        const int32_t o0 = offs[i];
-        const int32_t len = offs[i + 1] - o0;
-        const char* p = data + o0;
-        /* short keys: keep the bytes read for the hash in two registers
-         * (lo = bytes 0..7, hi = bytes 8..15) for the inline verify */
-        uint64_t klo = 0, khi = 0, fp;
-        if ((uint32_t)len <= INTERN_INLINE_MAX) {
-            fp = 1469598103934665603ULL;
-            const int32_t n0 = len < 8 ? len : 8;
-            for (int32_t j = 0; j < n0; j++) {
-                const uint64_t b = (uint8_t)p[j];
-                fp = (fp ^ b) * 1099511628211ULL;
-                klo |= b << (8 * j);
+     * and lookup return at once when the stamp is not theirs.
+     *
+     * The block walks tiles of BLOCK consecutive rows (block-uniform loop:
+     * the body has barriers). A tile's keys are one contiguous span of the
+     * utf8 column: its offsets are read once into LDS, and a span of at most
+     * INTERN_STAGE_BYTES is copied into LDS with aligned, coalesced 16 B
+     * loads — only granules holding at least one byte of the span, so the
+     * copy never leaves a page the column is on. Each lane then hashes its
+     * key from LDS. A tile with a longer span hashes from global memory. */
+    __shared__ int32_t s_offs[BLOCK + 1];
+    __shared__ uint4 s_stage[INTERN_STAGE_GRAN];
+    const int t = threadIdx.x;
+    const int64_t ntiles = (n + BLOCK - 1) / BLOCK;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t i0 = tile * BLOCK;
+        const int rows = (int)i64min(BLOCK, n - i0);
+        if (t < rows) s_offs[t] = offs[i0 + t];
+        if (t == 0) s_offs[rows] = offs[i0 + rows];
+        __syncthreads();
+        const int32_t o_first = s_offs[0];
+        const uint32_t span = (uint32_t)(s_offs[rows] - o_first);
+        const bool staged = span <= (uint32_t)INTERN_STAGE_BYTES;
+        uint32_t head = 0;
+        if (staged) {
+            if (span) {
+                const char* a0 = data + o_first;
+                head = (uint32_t)((uintptr_t)a0 & 15u);
+                const uint4* g = (const uint4*)(a0 - head);
+                const uint32_t ngran = (head + span + 15u) >> 4;
+                for (uint32_t k = t; k < ngran; k += BLOCK) s_stage[k] = g[k];
             }
-            for (int32_t j = 8; j < len; j++) {
-                const uint64_t b = (uint8_t)p[j];
-                fp = (fp ^ b) * 1099511628211ULL;
-                khi |= b << (8 * (j - 8));
-            }
-        } else {
-            fp = fnv1a64(p, len);
+            __syncthreads();
         }
+        const bool active = t < rows;
+        const int64_t i = i0 + t;
+        int32_t o0 = 0, len = 0;
+        uint64_t klo = 0, khi = 0, fp = 0;
+        if (active) {
+            o0 = s_offs[t];
+            len = s_offs[t + 1] - o0;
+            if (staged) {
+                const uint32_t q = head + (uint32_t)(o0 - o_first);
+                fp = key_fp_bytes((const uint8_t*)s_stage + q, len, &klo,
+                                  &khi);
+            } else {
+                fp = key_fp_bytes((const uint8_t*)data + o0, len, &klo, &khi);
+            }
+        }
+        /* every LDS read of this tile is done: the next tile may overwrite
+         * the stage while slower lanes are still probing */
+        __syncthreads();
+        if (!active) continue;
+        const char* p = data + o0;
         fp &= fp_mask; /* all-ones outside the collision tests */
         if (!fp) fp = 1; /* 0 marks an empty slot */
         uint32_t slot = (uint32_t)fp & p_mask;
