@@ -523,8 +523,9 @@ class JoinOp:
                                                   d_vals), "push_probe")
 
     def matches(self):
-        """(n, d_ts, d_kid32, d_vals) of the LAST push — device pointers,
-        valid until the second-next push on this op."""
+        """(n, d_ts, d_kid32, d_vals) of the LAST push (n == 0: no matches).
+        The columns of a push with matches stay valid until the push after
+        the next push with matches; zero-match pushes recycle nothing."""
         n = ctypes.c_int64()
         ts = ctypes.c_void_p()
         kid = ctypes.c_void_p()

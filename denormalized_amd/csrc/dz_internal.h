@@ -294,10 +294,19 @@ void launch_gen_json(hipStream_t stream, uint64_t seed, int64_t t0,
                      const int64_t* d_offs, char* d_data);
 
 /* stream join (cfg5): open-address trip->driver build table + stable
- * order-preserving probe/emit (kernels.hip §stream join) */
+ * order-preserving probe/emit (kernels.hip §stream join). d_pre is four
+ * cells the host zeroes per build push: the pre-pass writes {reserved trip
+ * seen, driver id out of int32 range seen, rows whose trip is not in the
+ * table (an upper bound: in-batch duplicates each count)}, the build adds
+ * the slots it claimed to d_pre[3]. */
+void launch_join_precheck(hipStream_t stream, const int64_t* d_trips,
+                          const int64_t* d_drivers, int64_t n,
+                          const int64_t* tab_trip, uint64_t p_mask,
+                          uint32_t* d_pre);
 void launch_join_build(hipStream_t stream, const int64_t* d_trips,
                        const int64_t* d_drivers, int64_t n, int64_t* tab_trip,
-                       int64_t* tab_drv, uint64_t p_mask, uint32_t* d_dbg);
+                       int64_t* tab_drv, uint64_t p_mask, uint32_t* d_dbg,
+                       uint32_t* d_pre);
 void launch_join_probe(hipStream_t stream, const int64_t* d_ts,
                        const int64_t* d_trips, const double* d_vals, int64_t n,
                        int64_t chunk, int C, const int64_t* tab_trip,

@@ -1767,13 +1767,54 @@ __device__ __forceinline__ uint64_t jhash(int64_t trip) {
     return (uint64_t)trip * 0x9e3779b97f4a7c15ULL;
 }
 
-__global__ void k_join_build(const int64_t* trips, const int64_t* drivers,
-                             int64_t n, int64_t* tab_trip, int64_t* tab_drv,
-                             uint64_t p_mask, uint32_t* dbg) {
+/* build pre-pass (validate BEFORE any write): pre[0] flags a trip equal to
+ * the empty-slot sentinel, pre[1] a driver id outside [0, INT32_MAX], and
+ * pre[2] counts rows whose trip is not in the table yet. Duplicates of a
+ * new trip within the batch each count: the figure is an upper bound on the
+ * slots the build will claim, which is what the capacity check needs. */
+__global__ void k_join_precheck(const int64_t* trips, const int64_t* drivers,
+                                int64_t n, const int64_t* tab_trip,
+                                uint64_t p_mask, uint32_t* pre) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    uint32_t fresh = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += stride) {
         const int64_t trip = trips[i];
+        const int64_t drv = drivers[i];
+        if (trip == JEMPTY) {
+            pre[0] = 1;
+            continue;
+        }
+        if (drv < 0 || drv > (int64_t)INT32_MAX) pre[1] = 1;
+        uint64_t slot = jhash(trip) & p_mask;
+        for (uint64_t probes = 0; probes <= p_mask; ++probes) {
+            const int64_t got = tab_trip[slot];
+            if (got == JEMPTY) {
+                fresh++;
+                break;
+            }
+            if (got == trip) break;
+            slot = (slot + 1) & p_mask;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1)
+        fresh += (uint32_t)__shfl_down((int)fresh, o);
+    if ((threadIdx.x & 63) == 0 && fresh) atomicAdd(&pre[2], fresh);
+}
+
+/* pre[3] receives the number of slots this batch claimed (the op keeps the
+ * running total for the capacity check). The host refuses a batch that would
+ * fill the table past half before this kernel runs; the probe bound is the
+ * second line of defence. */
+__global__ void k_join_build(const int64_t* trips, const int64_t* drivers,
+                             int64_t n, int64_t* tab_trip, int64_t* tab_drv,
+                             uint64_t p_mask, uint32_t* dbg, uint32_t* pre) {
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    uint32_t claimed = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const int64_t trip = trips[i];
+        if (trip == JEMPTY) continue; /* refused by the pre-pass */
         uint64_t slot = jhash(trip) & p_mask;
         for (uint64_t probes = 0;; slot = (slot + 1) & p_mask) {
             int64_t got = tab_trip[slot];
@@ -1781,7 +1822,10 @@ __global__ void k_join_build(const int64_t* trips, const int64_t* drivers,
                 got = (int64_t)atomicCAS((unsigned long long*)&tab_trip[slot],
                                          (unsigned long long)JEMPTY,
                                          (unsigned long long)trip);
-                if (got == JEMPTY) got = trip; /* claimed */
+                if (got == JEMPTY) {
+                    got = trip; /* claimed */
+                    claimed++;
+                }
             }
             if (got == trip) {
                 /* later duplicates overwrite (dimension update); the winner
@@ -1796,10 +1840,16 @@ __global__ void k_join_build(const int64_t* trips, const int64_t* drivers,
             }
         }
     }
+    for (int o = 32; o > 0; o >>= 1)
+        claimed += (uint32_t)__shfl_down((int)claimed, o);
+    if ((threadIdx.x & 63) == 0 && claimed) atomicAdd(&pre[3], claimed);
 }
 
 /* probe pass 1: resolve each row's driver (or -1) into drv_tmp and count
- * matches per chunk (one block per chunk) */
+ * matches per chunk (one block per chunk). The empty test comes first, so a
+ * probe row whose trip IS the sentinel stops at the first empty slot
+ * unmatched instead of "matching" it; the walk is bounded by the table size
+ * whatever the table holds. */
 __global__ __launch_bounds__(64) void k_join_mark(const int64_t* trips,
         int64_t n, int64_t chunk, const int64_t* tab_trip,
         const int64_t* tab_drv, uint64_t p_mask, int32_t* drv_tmp,
@@ -1811,13 +1861,14 @@ __global__ __launch_bounds__(64) void k_join_mark(const int64_t* trips,
         const int64_t trip = trips[i];
         uint64_t slot = jhash(trip) & p_mask;
         int32_t drv = -1;
-        for (;;) {
+        /* at most 2^28 slots: a 32-bit countdown covers the whole table */
+        for (uint32_t left = (uint32_t)p_mask + 1u; left; --left) {
             const int64_t got = tab_trip[slot];
+            if (got == JEMPTY) break;
             if (got == trip) {
                 drv = (int32_t)tab_drv[slot];
                 break;
             }
-            if (got == JEMPTY) break;
             slot = (slot + 1) & p_mask;
         }
         drv_tmp[i] = drv;
@@ -1903,13 +1954,24 @@ void launch_fill_i64(hipStream_t s, int64_t* d_p, int64_t n, int64_t v) {
     hipLaunchKernelGGL(k_fill_i64, dim3(blocks), dim3(BLOCK), 0, s, d_p, n, v);
 }
 
+void launch_join_precheck(hipStream_t s, const int64_t* d_trips,
+                          const int64_t* d_drivers, int64_t n,
+                          const int64_t* tab_trip, uint64_t p_mask,
+                          uint32_t* d_pre) {
+    int blocks = (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_join_precheck, dim3(blocks), dim3(BLOCK), 0, s,
+                       d_trips, d_drivers, n, tab_trip, p_mask, d_pre);
+}
+
 void launch_join_build(hipStream_t s, const int64_t* d_trips,
                        const int64_t* d_drivers, int64_t n, int64_t* tab_trip,
-                       int64_t* tab_drv, uint64_t p_mask, uint32_t* d_dbg) {
+                       int64_t* tab_drv, uint64_t p_mask, uint32_t* d_dbg,
+                       uint32_t* d_pre) {
     int blocks = (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048);
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_join_build, dim3(blocks), dim3(BLOCK), 0, s, d_trips,
-                       d_drivers, n, tab_trip, tab_drv, p_mask, d_dbg);
+                       d_drivers, n, tab_trip, tab_drv, p_mask, d_dbg, d_pre);
 }
 
 void launch_join_probe(hipStream_t s, const int64_t* d_ts,

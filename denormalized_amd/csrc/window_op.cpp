@@ -2883,27 +2883,35 @@ struct dz_join_op {
     int64_t* tab_trip = nullptr; /* open-address (trip -> driver), JEMPTY=empty */
     int64_t* tab_drv = nullptr;
     uint64_t p_mask = 0;
+    /* slots claimed so far. Build pushes keep it at or below half the slots
+     * (refused before they write otherwise), so every probe walk meets an
+     * empty slot. */
+    int64_t n_claimed = 0;
+    int64_t n_trips_hint = 0;
     /* unmatched ping-pong buffers (order-preserving) */
     int64_t* u_ts[2] = {};
     int64_t* u_trip[2] = {};
     double* u_val[2] = {};
     int64_t u_cap = 0, u_n = 0;
     int u_cur = 0;
-    /* matched output, double-buffered: buffer b stays valid until the
-     * SECOND-next push on the join op (a window op's borrowed push reads
-     * it until the window's next call) */
+    /* matched output, double-buffered. Only a push that produces matches
+     * flips o_cur, and growth regrows only the buffer the push writes (each
+     * has its own capacity): o_cur's columns stay valid, at the pointers
+     * dz_join_op_matches returned, until the push after the next push with
+     * matches (a window op's borrowed push reads them until the window's
+     * next call) */
     int64_t* o_ts[2] = {};
     int32_t* o_kid[2] = {};
     double* o_val[2] = {};
-    int64_t o_cap = 0;
+    int64_t o_cap[2] = {0, 0};
     int o_cur = 0;
     int64_t o_n = 0;
     /* probe scratch */
     int32_t* d_drvtmp = nullptr;
     int64_t drv_cap = 0;
     uint32_t* d_jcnt = nullptr;  /* [512] counts + mbase + ubase + tot */
-    uint32_t* h_tot = nullptr;   /* pinned {matched, unmatched} */
-    uint32_t* d_dbg = nullptr;
+    uint32_t* h_tot = nullptr;   /* pinned {matched, unmatched} + pre[4] */
+    uint32_t* d_dbg = nullptr;   /* [0..3] guard cells, [4..7] build pre-pass */
 };
 
 extern "C" void dz_join_op_destroy(dz_join_op* op);
@@ -2926,6 +2934,7 @@ extern "C" dz_join_op* dz_join_op_create(int32_t device, int64_t n_trips_hint) {
     }
     auto* op = new dz_join_op();
     op->device = device;
+    op->n_trips_hint = n_trips_hint;
     uint64_t want = 4 * (uint64_t)std::max<int64_t>(n_trips_hint, 1);
     uint64_t P = 1u << 16;
     while (P < want && P < (1ull << 28)) P <<= 1;
@@ -2935,13 +2944,13 @@ extern "C" dz_join_op* dz_join_op_create(int32_t device, int64_t n_trips_hint) {
         hipMalloc(&op->tab_trip, P * 8) != hipSuccess ||
         hipMalloc(&op->tab_drv, P * 8) != hipSuccess ||
         hipMalloc(&op->d_jcnt, (3 * 512 + 2) * 4) != hipSuccess ||
-        hipMalloc(&op->d_dbg, 16) != hipSuccess ||
-        hipHostMalloc((void**)&op->h_tot, 8) != hipSuccess) {
+        hipMalloc(&op->d_dbg, 32) != hipSuccess ||
+        hipHostMalloc((void**)&op->h_tot, 32) != hipSuccess) {
         g_err = "join op allocation failed";
         dz_join_op_destroy(op); /* frees whatever was allocated */
         return nullptr;
     }
-    hipMemset(op->d_dbg, 0, 16);
+    hipMemset(op->d_dbg, 0, 32);
     dz::launch_fill_i64(op->stream, op->tab_trip, (int64_t)P, INT64_MIN);
     if (hipStreamSynchronize(op->stream) != hipSuccess) {
         g_err = "join table init failed";
@@ -2971,29 +2980,39 @@ extern "C" const char* dz_join_last_error(dz_join_op* op) {
     return op->err.empty() ? nullptr : op->err.c_str();
 }
 
+/* Output buffer b must hold `need` rows (a probe's batch, or a full buffer
+ * re-probe). Growth regrows ONLY b, the buffer this push writes. The other
+ * one holds the last matches, which a downstream window op still reads at
+ * its next call (borrowed-push contract; that read is not even enqueued
+ * yet, so no barrier could cover freeing it). b held the output before
+ * last, whose consumer kernels may still be in flight on the window op's
+ * streams, not ours: full-device barrier before the free. */
+static dz_status join_ensure_out(dz_join_op* op, int b, int64_t need) {
+    if (need <= op->o_cap[b]) return DZ_OK;
+    if (op->o_cap[b] > 0) JCHK(op, hipDeviceSynchronize());
+    hipFree(op->o_ts[b]); hipFree(op->o_kid[b]); hipFree(op->o_val[b]);
+    op->o_ts[b] = nullptr;
+    op->o_kid[b] = nullptr;
+    op->o_val[b] = nullptr;
+    op->o_cap[b] = 0;
+    JCHK(op, hipMalloc(&op->o_ts[b], (size_t)need * 8));
+    JCHK(op, hipMalloc(&op->o_kid[b], (size_t)need * 4));
+    JCHK(op, hipMalloc(&op->o_val[b], (size_t)need * 8));
+    op->o_cap[b] = need;
+    return DZ_OK;
+}
+
+/* mark scratch for max(n, u_n) rows (the buffer re-probe on a build push
+ * marks u_n rows, not n) and room for n more unmatched rows */
 static dz_status join_ensure_probe(dz_join_op* op, int64_t n) {
-    /* the buffer re-probe on a build push marks u_n rows, not n */
     int64_t need_drv = std::max(n, op->u_n);
     if (need_drv > op->drv_cap) {
         JCHK(op, hipStreamSynchronize(op->stream));
         hipFree(op->d_drvtmp);
+        op->d_drvtmp = nullptr;
+        op->drv_cap = 0;
         JCHK(op, hipMalloc(&op->d_drvtmp, (size_t)need_drv * 4));
         op->drv_cap = need_drv;
-    }
-    /* output must hold this probe's matches OR a full buffer re-probe.
-     * GROWTH frees buffers a downstream window op may still be reading
-     * under the borrowed-push contract (its streams, not ours): take a
-     * full-device barrier before freeing. */
-    int64_t need_o = std::max(n, op->u_n);
-    if (need_o > op->o_cap) {
-        JCHK(op, hipDeviceSynchronize());
-        for (int i = 0; i < 2; i++) {
-            hipFree(op->o_ts[i]); hipFree(op->o_kid[i]); hipFree(op->o_val[i]);
-            JCHK(op, hipMalloc(&op->o_ts[i], (size_t)need_o * 8));
-            JCHK(op, hipMalloc(&op->o_kid[i], (size_t)need_o * 4));
-            JCHK(op, hipMalloc(&op->o_val[i], (size_t)need_o * 8));
-        }
-        op->o_cap = need_o;
     }
     int64_t need_u = op->u_n + n;
     if (need_u > op->u_cap) {
@@ -3030,24 +3049,74 @@ static dz_status join_check_dbg(dz_join_op* op) {
     return DZ_OK;
 }
 
+/* Validate a build batch BEFORE it writes anything (pre-pass kernel over the
+ * batch): a refusal leaves the table, the unmatched buffer and the last
+ * matches exactly as they were, and the handle stays usable. */
+static dz_status join_validate_build(dz_join_op* op, int64_t n,
+                                     const int64_t* d_trip_ids,
+                                     const int64_t* d_driver_ids) {
+    if (n >= (1LL << 31)) {
+        op->err = "build batch exceeds 2^31 rows; push smaller batches";
+        return DZ_ERR;
+    }
+    uint32_t* d_pre = op->d_dbg + 4;
+    uint32_t* h_pre = op->h_tot + 2;
+    JCHK(op, hipMemsetAsync(d_pre, 0, 16, op->stream));
+    dz::launch_join_precheck(op->stream, d_trip_ids, d_driver_ids, n,
+                             op->tab_trip, op->p_mask, d_pre);
+    JCHK(op, hipMemcpyAsync(h_pre, d_pre, 16, hipMemcpyDeviceToHost,
+                            op->stream));
+    JCHK(op, hipStreamSynchronize(op->stream));
+    if (h_pre[0]) {
+        op->err = "join build batch refused: it holds the reserved trip id "
+                  "INT64_MIN (the table's empty-slot mark); nothing written";
+        return DZ_ERR;
+    }
+    if (h_pre[1]) {
+        op->err = "join build batch refused: it holds a driver id outside "
+                  "the int32 range [0, 2147483647]; nothing written";
+        return DZ_ERR;
+    }
+    /* h_pre[2] counts each in-batch duplicate of a new trip: conservative */
+    const int64_t cap = (int64_t)((op->p_mask + 1) / 2);
+    if (op->n_claimed + (int64_t)h_pre[2] > cap) {
+        op->err = "join build batch refused: capacity — " +
+                  std::to_string(op->n_claimed) + " trips held + " +
+                  std::to_string(h_pre[2]) + " new rows exceed " +
+                  std::to_string(cap) + " (half the table's slots); raise "
+                  "n_trips_hint (" + std::to_string(op->n_trips_hint) +
+                  "); nothing written";
+        return DZ_ERR;
+    }
+    return DZ_OK;
+}
+
 extern "C" dz_status dz_join_op_push_build(dz_join_op* op, int64_t n,
                                            const int64_t* d_trip_ids,
                                            const int64_t* d_driver_ids) {
     if (!op) return DZ_ERR;
     JCHK(op, hipSetDevice(op->device));
-    op->o_n = 0;
-    if (n > 0)
+    if (n > 0) {
+        if (join_validate_build(op, n, d_trip_ids, d_driver_ids) != DZ_OK)
+            return DZ_ERR;
         dz::launch_join_build(op->stream, d_trip_ids, d_driver_ids, n,
-                              op->tab_trip, op->tab_drv, op->p_mask, op->d_dbg);
+                              op->tab_trip, op->tab_drv, op->p_mask, op->d_dbg,
+                              op->d_dbg + 4);
+        JCHK(op, hipMemcpyAsync(op->h_tot + 5, op->d_dbg + 7, 4,
+                                hipMemcpyDeviceToHost, op->stream));
+    }
+    op->o_n = 0;
     if (op->u_n > 0) {
         /* re-probe the unmatched buffer: newly matched rows emit in their
          * original buffered order; the rest compact into the other buffer */
-        if (join_ensure_probe(op, 0) != DZ_OK) return DZ_ERR;
+        const int nxt = op->o_cur ^ 1;
+        if (join_ensure_probe(op, 0) != DZ_OK ||
+            join_ensure_out(op, nxt, op->u_n) != DZ_OK)
+            return DZ_ERR;
         const int src = op->u_cur, dst = src ^ 1;
         int C = (int)std::min<int64_t>(512,
                                        std::max<int64_t>(1, (op->u_n + 8191) / 8192));
         int64_t chunk = (op->u_n + C - 1) / C;
-        const int nxt = op->o_cur ^ 1;
         dz::launch_join_probe(op->stream, op->u_ts[src], op->u_trip[src],
                               op->u_val[src], op->u_n, chunk, C, op->tab_trip,
                               op->tab_drv, op->p_mask, op->d_drvtmp,
@@ -3058,13 +3127,15 @@ extern "C" dz_status dz_join_op_push_build(dz_join_op* op, int64_t n,
         JCHK(op, hipMemcpyAsync(op->h_tot, op->d_jcnt + 1536, 8,
                                 hipMemcpyDeviceToHost, op->stream));
         JCHK(op, hipStreamSynchronize(op->stream));
-        op->o_cur = nxt;
+        /* a re-probe that releases nothing keeps the last matches current */
+        if (op->h_tot[0] > 0) op->o_cur = nxt;
         op->o_n = op->h_tot[0];
         op->u_n = op->h_tot[1];
         op->u_cur = dst;
     } else {
         JCHK(op, hipStreamSynchronize(op->stream));
     }
+    if (n > 0) op->n_claimed += op->h_tot[5];
     return join_check_dbg(op);
 }
 
@@ -3076,10 +3147,12 @@ extern "C" dz_status dz_join_op_push_probe(dz_join_op* op, int64_t n,
     JCHK(op, hipSetDevice(op->device));
     op->o_n = 0;
     if (n <= 0) return DZ_OK;
-    if (join_ensure_probe(op, n) != DZ_OK) return DZ_ERR;
+    const int nxt = op->o_cur ^ 1;
+    if (join_ensure_probe(op, n) != DZ_OK ||
+        join_ensure_out(op, nxt, n) != DZ_OK)
+        return DZ_ERR;
     int C = (int)std::min<int64_t>(512, std::max<int64_t>(1, (n + 8191) / 8192));
     int64_t chunk = (n + C - 1) / C;
-    const int nxt = op->o_cur ^ 1;
     const int ub = op->u_cur;
     dz::launch_join_probe(op->stream, d_ts_ms, d_trip_ids, d_vals, n, chunk, C,
                           op->tab_trip, op->tab_drv, op->p_mask, op->d_drvtmp,
@@ -3090,15 +3163,20 @@ extern "C" dz_status dz_join_op_push_probe(dz_join_op* op, int64_t n,
     JCHK(op, hipMemcpyAsync(op->h_tot, op->d_jcnt + 1536, 8,
                             hipMemcpyDeviceToHost, op->stream));
     JCHK(op, hipStreamSynchronize(op->stream));
-    op->o_cur = nxt;
+    /* a probe that matches nothing wrote nothing: keep the last matches
+     * current, a consumer may still hold them staged */
+    if (op->h_tot[0] > 0) op->o_cur = nxt;
     op->o_n = op->h_tot[0];
     op->u_n += op->h_tot[1];
     return join_check_dbg(op);
 }
 
-/* matched output of the LAST push (device-resident). Valid until the
- * SECOND-next push on this join op (double-buffered), which covers a
- * dz_window_op borrowed push consuming it across one pipeline step. */
+/* matched output of the LAST push (device-resident); n == 0 when it produced
+ * none. The columns of a push with matches stay valid, at these pointers,
+ * until the push AFTER the next push with matches: pushes with zero matches
+ * recycle nothing, and growth regrows only the buffer a push writes. That
+ * covers a dz_window_op borrowed push, skipped when n == 0, consuming them
+ * across one pipeline step. */
 extern "C" dz_status dz_join_op_matches(dz_join_op* op, int64_t* n_out,
                                         const int64_t** d_ts,
                                         const int32_t** d_kid,

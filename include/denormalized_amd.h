@@ -249,9 +249,21 @@ dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
  * in row order and re-emit (original order) when their build row arrives;
  * rows never matched are dropped (inner join). Outputs are device-resident
  * (ts, driver id as a dense int32 key, value) columns shaped for a
- * zero-copy dz_window_op_push_device_borrowed — driver ids must fit int32.
- * Build-table capacity is sized from n_trips_hint (4x, pow2) and overflow
- * fails loudly. */
+ * zero-copy dz_window_op_push_device_borrowed.
+ *
+ * Capacity: the table has max(65536, pow2 >= 4 * n_trips_hint) slots (at most
+ * 2^28) and holds at most HALF of them, so at least 2 * n_trips_hint and
+ * never fewer than 32768 distinct trips. A build push is validated before it
+ * writes anything and is refused with DZ_ERR, one message per cause, when
+ *  - trips held + rows whose trip is new would exceed that capacity (rows
+ *    repeating a new trip within the batch each count, so a batch with such
+ *    duplicates can be refused slightly early; updates of trips already held
+ *    always pass);
+ *  - a trip id equals INT64_MIN, which is reserved (the empty-slot mark);
+ *  - a driver id lies outside [0, INT32_MAX] (the output kid column is int32).
+ * A refused push leaves the table, the unmatched buffer and the last matches
+ * exactly as they were; the handle stays usable. A PROBE row whose trip id is
+ * INT64_MIN is legal and never matches: it buffers like any absent trip. */
 
 typedef struct dz_join_op dz_join_op;
 
@@ -272,9 +284,16 @@ dz_status dz_join_op_push_probe(dz_join_op* op, int64_t n_rows,
                                 const int64_t* d_trip_ids,
                                 const double* d_vals);
 
-/* The LAST push's matched rows (device pointers, valid until the
- * second-next push on this op — double-buffered so a window op's borrowed
- * push can consume them across one pipeline step). */
+/* The LAST push's matched rows; n_out == 0 when it produced none (the
+ * pointers then still name the last non-empty output). The device columns of
+ * a push that produced matches stay valid and unchanged, at the pointers
+ * returned here, until the push AFTER the next push that produces matches:
+ * the output is double-buffered, a push with zero matches recycles nothing,
+ * and a push that needs more room regrows only the buffer it writes. So
+ *     if (n) dz_window_op_push_device_borrowed(...)
+ * after every join push always hands the window op live columns for its
+ * one-step borrowed lifetime, whatever the batch sizes and however many
+ * empty pushes intervene. */
 dz_status dz_join_op_matches(dz_join_op* op, int64_t* n_out,
                              const int64_t** d_ts_ms, const int32_t** d_kids,
                              const double** d_vals);

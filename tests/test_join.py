@@ -152,9 +152,12 @@ def test_device_join_matches_oracle():
 @pytest.mark.gpu
 def test_join_window_pipeline_matches_oracle():
     """cfg5 shape end to end ON DEVICE: probe batches join on trip_id, the
-    matched (ts, driver, reading) columns feed the window op ZERO-COPY
-    (borrowed push), 1s tumbling group-by driver; the oracle runs the same
-    pipeline (join restatement -> window restatement). Bit-exact."""
+    matched (ts, driver, reading) columns feed the window op through its
+    STAGING push (device-to-device copy), 1s tumbling group-by driver; the
+    oracle runs the same pipeline (join restatement -> window restatement).
+    Bit-exact. The zero-copy composition (borrowed push, as bench.py --cfg5)
+    is pinned by tests/test_join_edges_gpu.py::
+    test_borrowed_pipeline_with_varying_batches."""
     import __graft_entry__ as graft
     graft.build()
     from denormalized_amd import DeviceArray, JoinOp, WindowOp, _lib
