@@ -452,6 +452,14 @@ struct dz_window_op {
     std::atomic<uint64_t> e_builds{0};
     std::atomic<uint64_t> e_zc_builds{0};   /* zero-copy vs materializing */
     std::atomic<uint64_t> e_copy_builds{0}; /* device-path builds */
+    /* route counters (push thread writes, kernel_stats reads): group-batched
+     * chains enqueued, the closes they carried and the largest one; device
+     * per-close chains; per-close chains sorted by the single-block kernel */
+    std::atomic<uint64_t> e_group_chains{0};
+    std::atomic<uint64_t> e_group_closes{0};
+    std::atomic<uint64_t> e_group_max{0};
+    std::atomic<uint64_t> e_perclose_chains{0};
+    std::atomic<uint64_t> e_small_sorts{0};
     std::mutex out_mtx;             /* guards outq */
 
     /* filter pushdown */
@@ -1522,6 +1530,10 @@ static dz_status enqueue_group_device(dz_window_op* op, const Closed* cl,
         }
     }
     op->e_cv.notify_all();
+    op->e_group_chains++;
+    op->e_group_closes += (uint64_t)gcount;
+    if ((uint64_t)gcount > op->e_group_max.load())
+        op->e_group_max = (uint64_t)gcount;
     return DZ_OK;
 }
 
@@ -1685,11 +1697,13 @@ static dz_status enqueue_per_close(dz_window_op* op, const Closed* cl,
                  * live-count clamps in the multi-block chain won instead */
                 return v ? (uint32_t)atoi(v) : 0u;
             }();
+            op->e_perclose_chains++;
             if (small_max &&
-                op->e_nt_hint.load(std::memory_order_relaxed) <= small_max)
+                op->e_nt_hint.load(std::memory_order_relaxed) <= small_max) {
                 dz::launch_esort_small(cs, d.fkeys, d.skeys, d.fiota, d.okid,
                                        d.counter + 1, maxk);
-            else
+                op->e_small_sorts++;
+            } else
                 dz::launch_emission_sort(cs, op->n_keys, d.fkeys,
                                          d.skeys, d.fiota, d.okid,
                                          d.counter + 1, op->d_rhist[csi],
@@ -2801,6 +2815,11 @@ extern "C" dz_status dz_window_op_kernel_stats(dz_window_op* op,
         s.ms = op->e_build_ns.load() / 1e6;
         op->stats["h_emit_zc"].launches = op->e_zc_builds.load();
         op->stats["h_emit_copybuild"].launches = op->e_copy_builds.load();
+        op->stats["h_emit_group"].launches = op->e_group_chains.load();
+        op->stats["h_emit_group_closes"].launches = op->e_group_closes.load();
+        op->stats["h_emit_group_max"].launches = op->e_group_max.load();
+        op->stats["h_emit_perclose"].launches = op->e_perclose_chains.load();
+        op->stats["h_emit_smallsort"].launches = op->e_small_sorts.load();
     }
     int32_t n = 0;
     for (auto& kv : op->stats) {

@@ -126,10 +126,14 @@ def test_packed_paths_all_columns(stream, kind):
     outs, stats = _run(stream, kind)
     assert [b["n_rows"] for b in outs] == [NK, NK, NK, TAIL_KEYS]
     _assert_all_columns(stream, outs, kind)
-    # the per-close chain's two builds are counted by the engine; the
-    # group-batched chain has no counter — its coverage rests on the stream's
-    # construction (two closes in the first trigger, cold passer hint, NK >
-    # the 65,536 group threshold, slices > the 16,384 view threshold)
+    # the engine counts every route: the first trigger's two closes (cold
+    # passer hint, NK > the 65,536 group threshold, slices > the 16,384 view
+    # threshold) share ONE group-batched chain; windows 2 and 3 each take a
+    # per-close chain, whose two builds are counted as well
+    assert stats["h_emit_group"]["launches"] == 1
+    assert stats["h_emit_group_closes"]["launches"] == 2
+    assert stats["h_emit_perclose"]["launches"] == 2
+    assert stats["h_emit_smallsort"]["launches"] == 0
     assert stats["h_emit_zc"]["launches"] >= 1
     assert stats["h_emit_copybuild"]["launches"] >= 1
 
