@@ -111,6 +111,7 @@ def lib():
         except AttributeError:  # older engine build (A/B hook)
             pass
         L.dz_window_op_push_device_utf8.argtypes = [p, i64, p, p, p, p]
+        L.dz_window_op_push_device_i64.argtypes = [p, i64, p, p, p]
         L.dz_generate_utf8.argtypes = [ctypes.c_int32, ctypes.c_uint64, i64,
                                        i64, i64, p, p, p]
         L.dz_window_op_poll.argtypes = [p, ctypes.POINTER(ctypes.POINTER(DzOutBatch))]
@@ -288,9 +289,18 @@ class WindowOp:
             self._h, n, d_ts, d_key_offsets, d_key_data, d_vals),
             "push_device_utf8")
 
+    def push_device_i64(self, n, d_ts, d_keys, d_vals):
+        """Arbitrary int64 keys interned ON DEVICE; every int64 value is a
+        legal key. Borrowed semantics: the three buffers stay valid and
+        unmodified until the next call on the op. Requires key_kind
+        KEY_INT64 and an 8-byte-aligned d_keys."""
+        self._check(self._L.dz_window_op_push_device_i64(
+            self._h, n, d_ts, d_keys, d_vals), "push_device_i64")
+
     def debug_intern_fp_bits(self, bits):
-        """Test hook: mask intern fingerprints to `bits` bits (forces
-        collisions). Only before the first push_device_utf8."""
+        """Test hook: mask intern fingerprints (utf8) or key hashes (int64)
+        to `bits` bits: forces collisions / long probe chains. Only before
+        the first push_device_utf8 / push_device_i64."""
         self._check(self._L.dz_debug_intern_fp_bits(self._h, bits),
                     "debug_intern_fp_bits")
 

@@ -67,6 +67,17 @@ void launch_intern(hipStream_t stream, const int32_t* d_offs, const char* d_data
                    uint64_t fp_mask /* all-ones outside collision tests */,
                    uint32_t* d_dbg);
 
+/* device int64 intern: the same three phases for arbitrary int64 keys */
+void launch_intern_i64(hipStream_t stream, const int64_t* d_keys, int64_t n,
+                       uint4* tab /* p_mask + 2 16 B slots {key, id, row}:
+                                   * the table, then the key-0 cell */,
+                       uint32_t p_mask, int64_t* ikeys /* id_cap keys by id */,
+                       uint32_t* ctrs /* next id, unused, fresh-batch seq */,
+                       uint32_t id_cap, int32_t* out_kid,
+                       uint32_t seq /* this batch's number, never 0 */,
+                       uint64_t fp_mask /* masks the hash, not the key */,
+                       uint32_t* d_dbg);
+
 /* synthetic utf8 key generator ("sensor_{k}"): lens pass and/or fill pass */
 void launch_gen_utf8(hipStream_t stream, uint64_t seed, int64_t start_row,
                      int64_t n, int64_t nkeys, int32_t* d_lens,

@@ -435,6 +435,143 @@ void launch_intern(hipStream_t s, const int32_t* d_offs, const char* d_data,
                        id_len, pool, out_kid, fresh_seq, seq, dbg);
 }
 
+/* ------------------------------------------------------------------ */
+/* device int64 intern — the same three stream-ordered phases for      */
+/* 8-byte keys. The key is its own identity: the claim word IS the     */
+/* key, so there is no fingerprint, no pool and no verify, and no two  */
+/* distinct keys can merge.                                            */
+/*                                                                     */
+/* slot: 16 B, 16 B-aligned, one uint4 = one probe load:               */
+/*   {claim lo, claim hi, id (~0 = unassigned), claiming row}          */
+/* The claim word is the CAS target, 0 = empty. Key 0 therefore cannot */
+/* live in the table: it owns the extra slot tab[P] behind the P table */
+/* slots, claimed by its own CAS (0 -> I64_ZERO_CLAIM) and never       */
+/* probed past. Every int64 value is a legal key.                      */
+/* home slot = splitmix64(key) & fp_mask & p_mask (fp_mask is all-ones */
+/* outside dz_debug_intern_fp_bits).                                   */
+/* ------------------------------------------------------------------ */
+
+constexpr uint64_t I64_ZERO_CLAIM = 1; /* claim word of the key-0 cell */
+
+__global__ __launch_bounds__(BLOCK) void k_intern_i64_claim(
+        const int64_t* keys, int64_t n, uint4* tab, uint32_t p_mask,
+        uint64_t fp_mask, int32_t* out_kid, uint32_t* fresh_seq, uint32_t seq,
+        uint32_t* dbg) {
+    /* phase 1: every row probes; exactly one row CASes each new key in and
+     * records itself as the claiming row (the one word of a slot this
+     * phase writes besides the claim word; nothing reads it back on
+     * device). No lane ever waits on another. A slot whose id is assigned
+     * was written whole by an earlier batch's assign: key equal -> out_kid
+     * is final. Rows of keys claimed in THIS batch store ~slot and stamp
+     * *fresh_seq; assign and lookup return at once otherwise. */
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const uint64_t key = (uint64_t)keys[i];
+        const bool zero = key == 0;
+        const uint64_t want = zero ? I64_ZERO_CLAIM : key;
+        /* the key-0 cell only ever holds 0 or I64_ZERO_CLAIM, so a key-0
+         * row leaves the loop in its first iteration */
+        uint32_t slot = zero ? p_mask + 1
+                             : (uint32_t)(splitmix64(key) & fp_mask) & p_mask;
+        int32_t out;
+        for (uint32_t probes = 0;; slot = (slot + 1) & p_mask) {
+            const uint4 a = tab[slot];
+            if (a.z != ~0u) {
+                if (slot_fp(a) == want) {
+                    out = (int32_t)a.z;
+                    break;
+                }
+                /* another key's slot: probe on */
+            } else {
+                /* empty, or claimed in this batch (ids are assigned after
+                 * this kernel): the claim word again as an aligned 8 B
+                 * ATOMIC load — the halves of the 16 B load above may tear
+                 * against a concurrent claim CAS — then the CAS */
+                uint64_t got = __hip_atomic_load(
+                    (const uint64_t*)tab + (size_t)slot * 2, __ATOMIC_RELAXED,
+                    __HIP_MEMORY_SCOPE_AGENT);
+                if (got == 0)
+                    got = (uint64_t)atomicCAS((unsigned long long*)&tab[slot],
+                                              0ULL, (unsigned long long)want);
+                if (got == 0 || got == want) {
+                    if (got == 0) ((uint32_t*)&tab[slot])[3] = (uint32_t)i;
+                    *fresh_seq = seq;
+                    out = ~(int32_t)slot;
+                    break;
+                }
+            }
+            if (++probes > p_mask) {
+                dbg[3] = 4; /* table full */
+                *fresh_seq = seq;
+                out = ~(int32_t)slot;
+                break;
+            }
+        }
+        out_kid[i] = out;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_intern_i64_assign(uint4* tab,
+        uint32_t n_slots, int64_t* ikeys, uint32_t* ctrs, uint32_t id_cap,
+        const uint32_t* fresh_seq, uint32_t seq, uint32_t* dbg) {
+    /* phase 2: one thread per slot (the key-0 cell is slot n_slots - 1);
+     * a slot claimed this batch gets a dense id, its key goes to
+     * ikeys[id] for the host mirror, then the slot's id is set. The only
+     * writer of ids; no reader runs concurrently. */
+    if (*fresh_seq != seq) return; /* nothing was claimed in this batch */
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t sl = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         sl < n_slots; sl += stride) {
+        const uint4 v = tab[sl];
+        const uint64_t w = slot_fp(v);
+        if (w == 0 || v.z != ~0u) continue;
+        const uint32_t nid = atomicAdd(&ctrs[0], 1u);
+        if (nid >= id_cap) {
+            dbg[3] = 1; /* capacity guard */
+            continue;
+        }
+        ikeys[nid] = sl == (int64_t)n_slots - 1 ? 0 : (int64_t)w;
+        ((uint32_t*)&tab[sl])[2] = nid;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_intern_i64_lookup(int64_t n,
+        const uint4* tab, int32_t* out_kid, const uint32_t* fresh_seq,
+        uint32_t seq, uint32_t* dbg) {
+    /* phase 3: resolve each ~slot stashed by the claim phase to its id */
+    if (*fresh_seq != seq) return; /* claim resolved every row */
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const int32_t v = out_kid[i];
+        if (v >= 0) continue; /* resolved by the claim phase: final */
+        const uint32_t cand = ((const uint32_t*)&tab[(uint32_t)~v])[2];
+        int32_t id = 0;
+        if (cand == ~0u) dbg[3] = 5; /* capacity overflow: unassigned */
+        else id = (int32_t)cand;
+        out_kid[i] = id;
+    }
+}
+
+void launch_intern_i64(hipStream_t s, const int64_t* d_keys, int64_t n,
+                       uint4* tab, uint32_t p_mask, int64_t* ikeys,
+                       uint32_t* ctrs, uint32_t id_cap, int32_t* out_kid,
+                       uint32_t seq, uint64_t fp_mask, uint32_t* dbg) {
+    int blocks = (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048);
+    if (blocks < 1) blocks = 1;
+    const uint32_t n_slots = p_mask + 2; /* the table + the key-0 cell */
+    int sblocks = (int)std::min<uint32_t>((n_slots + BLOCK - 1) / BLOCK, 2048);
+    uint32_t* fresh_seq = ctrs + 2;
+    hipLaunchKernelGGL(k_intern_i64_claim, dim3(blocks), dim3(BLOCK), 0, s,
+                       d_keys, n, tab, p_mask, fp_mask, out_kid, fresh_seq,
+                       seq, dbg);
+    hipLaunchKernelGGL(k_intern_i64_assign, dim3(sblocks), dim3(BLOCK), 0, s,
+                       tab, n_slots, ikeys, ctrs, id_cap, fresh_seq, seq, dbg);
+    hipLaunchKernelGGL(k_intern_i64_lookup, dim3(blocks), dim3(BLOCK), 0, s,
+                       n, tab, out_kid, fresh_seq, seq, dbg);
+}
+
 /* synthetic utf8 key generator: "sensor_{k}" with k from the SAME splitmix
  * draw as the dense generator (spec in DESIGN.md §Generator) — lengths
  * first (host cumsums them into offsets), then the bytes */

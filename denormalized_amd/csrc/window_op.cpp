@@ -294,7 +294,14 @@ struct dz_window_op {
     uint32_t i_idcap = 0, i_poolcap = 0;
     int32_t* d_ikid[2] = {};        /* interned dense ids, per pipeline buf */
     int64_t i_kid_cap[2] = {0, 0};
-    int64_t mirror_keys = 0;        /* ids mirrored into dict_strs so far */
+    int64_t mirror_keys = 0;        /* ids mirrored into dict_strs (utf8) or
+                                     * dict_vals (int64) so far */
+    /* device int64 intern (DZ_KEY_INT64 ops): shares i_pmask, i_idcap,
+     * d_ictrs, i_seq, i_fpmask, d_ikid and mirror_keys with the utf8 intern
+     * (an op has one key kind) */
+    uint4* d_i64tab = nullptr;      /* 16 B slots {key, id, row}: the table,
+                                     * then the key-0 cell */
+    int64_t* d_ikeys = nullptr;     /* key by id, i_idcap entries */
 
     /* input staging (host-batch path) */
     int64_t* d_ts = nullptr;
@@ -495,6 +502,7 @@ static void emit_worker_main(dz_window_op* op);
 static dz_status ensure_emission(dz_window_op* op);
 static dz_status process_pending(dz_window_op* op);
 static dz_status intern_sync_mirror(dz_window_op* op);
+static dz_status intern_i64_sync_mirror(dz_window_op* op);
 
 static hipEvent_t get_event(dz_window_op* op) {
     if (!op->ev_pool.empty()) {
@@ -783,6 +791,7 @@ extern "C" void dz_window_op_destroy(dz_window_op* op) {
     hipFree(op->d_itab); hipFree(op->d_itab_row);
     hipFree(op->d_ioff); hipFree(op->d_ilen);
     hipFree(op->d_ipool); hipFree(op->d_ictrs);
+    hipFree(op->d_i64tab); hipFree(op->d_ikeys);
     hipFree(op->d_ikid[0]); hipFree(op->d_ikid[1]);
     hipFree(op->d_ts); hipFree(op->d_kid); hipFree(op->d_vals); hipFree(op->d_valbm);
     for (int i = 0; i < 2; i++) {
@@ -2233,6 +2242,8 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
     }
     if (op->d_itab && intern_sync_mirror(op) != DZ_OK)
         return DZ_ERR; /* newly interned key bytes -> emission dictionary */
+    if (op->d_i64tab && intern_i64_sync_mirror(op) != DZ_OK)
+        return DZ_ERR; /* newly interned int64 keys -> dict_vals */
     return trigger_windows(op);
 }
 
@@ -2331,6 +2342,18 @@ extern "C" dz_status dz_window_op_push_device_borrowed(
  * the rest of the pipeline sees dense int32 ids like every other path.  */
 /* ------------------------------------------------------------------ */
 
+/* the interned-id ring buffer the next push writes */
+static dz_status ensure_ikid(dz_window_op* op, int64_t n) {
+    int b = op->next_buf;
+    if (n > op->i_kid_cap[b]) {
+        quiesce(op);
+        hipFree(op->d_ikid[b]);
+        CHK(op, hipMalloc(&op->d_ikid[b], (size_t)n * 4));
+        op->i_kid_cap[b] = n;
+    }
+    return DZ_OK;
+}
+
 static dz_status ensure_intern(dz_window_op* op, int64_t n) {
     if (!op->d_itab) {
         uint64_t want = 4 * (uint64_t)std::max<int64_t>(op->kcap, 1);
@@ -2356,14 +2379,32 @@ static dz_status ensure_intern(dz_window_op* op, int64_t n) {
         /* the intern runs on i_stream: make the init visible there */
         CHK(op, hipStreamSynchronize(op->stream));
     }
-    int b = op->next_buf;
-    if (n > op->i_kid_cap[b]) {
-        quiesce(op);
-        hipFree(op->d_ikid[b]);
-        CHK(op, hipMalloc(&op->d_ikid[b], (size_t)n * 4));
-        op->i_kid_cap[b] = n;
+    return ensure_ikid(op, n);
+}
+
+/* int64 keys: one 16 B slot {key, id, row} per probe step, the key-0 cell
+ * behind the table, and the keys by id for the host mirror. Sized by the
+ * rule of ensure_intern. */
+static dz_status ensure_intern_i64(dz_window_op* op, int64_t n) {
+    if (!op->d_i64tab) {
+        uint64_t want = 4 * (uint64_t)std::max<int64_t>(op->kcap, 1);
+        uint32_t P = 1u << 16;
+        while (P < want && P < (1u << 26)) P <<= 1;
+        op->i_pmask = P - 1;
+        op->i_idcap = P / 2;
+        const size_t n_slots = (size_t)P + 1;
+        CHK(op, hipMalloc(&op->d_i64tab, n_slots * 16));
+        CHK(op, hipMalloc(&op->d_ikeys, (size_t)op->i_idcap * 8));
+        CHK(op, hipMalloc(&op->d_ictrs, 12));
+        /* key zero (empty), row zero, id ~0 (unassigned) */
+        CHK(op, hipMemsetAsync(op->d_i64tab, 0, n_slots * 16, op->stream));
+        CHK(op, hipMemset2DAsync((char*)op->d_i64tab + 8, 16, 0xFF, 4, n_slots,
+                                 op->stream));
+        CHK(op, hipMemsetAsync(op->d_ictrs, 0, 12, op->stream));
+        /* the intern runs on i_stream: make the init visible there */
+        CHK(op, hipStreamSynchronize(op->stream));
     }
-    return DZ_OK;
+    return ensure_ikid(op, n);
 }
 
 /* pull newly interned key bytes into the host dictionary mirror so the
@@ -2392,11 +2433,29 @@ static dz_status intern_sync_mirror(dz_window_op* op) {
     return DZ_OK;
 }
 
+/* the int64 analogue: keys of ids [mirror_keys, n_keys) -> dict_vals. Same
+ * call site, same ordering argument. */
+static dz_status intern_i64_sync_mirror(dz_window_op* op) {
+    if (op->mirror_keys >= op->n_keys) return DZ_OK;
+    int64_t lo = op->mirror_keys, hi = op->n_keys;
+    std::vector<int64_t> keys(hi - lo);
+    CHK(op, hipMemcpy(keys.data(), op->d_ikeys + lo, (size_t)(hi - lo) * 8,
+                      hipMemcpyDeviceToHost));
+    for (int64_t k : keys) op->dict_vals.push_back(k);
+    op->mirror_keys = hi;
+    return DZ_OK;
+}
+
 extern "C" dz_status dz_debug_intern_fp_bits(dz_window_op* op, int32_t bits) {
     if (!op) return DZ_ERR;
     if (op->d_itab) {
         op->err = "dz_debug_intern_fp_bits is legal only before the first "
                   "device utf8 push";
+        return DZ_ERR;
+    }
+    if (op->d_i64tab) {
+        op->err = "dz_debug_intern_fp_bits is legal only before the first "
+                  "device i64 push";
         return DZ_ERR;
     }
     if (bits < 1 || bits > 64) {
@@ -2444,6 +2503,55 @@ extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
                           op->i_pmask, op->d_ioff, op->d_ilen, op->d_ipool,
                           op->d_ictrs, op->i_idcap, op->i_poolcap,
                           op->d_ikid[b], op->i_seq, op->i_fpmask, op->d_dbg);
+    });
+    if (stage_core(op, n_rows, d_ts_ms, op->d_ikid[b], d_vals, nullptr,
+                   /*keys_are_dense=*/true, /*deferred=*/true,
+                   /*borrow=*/true) != DZ_OK)
+        return DZ_ERR;
+    if (prev.active) return process_batch(op, prev);
+    return DZ_OK;
+}
+
+/* device int64 push: arbitrary int64 keys interned on the ingest stream,
+ * then the dense-id pipeline, exactly as the utf8 push above */
+extern "C" dz_status dz_window_op_push_device_i64(dz_window_op* op,
+        int64_t n_rows, const int64_t* d_ts_ms, const int64_t* d_keys,
+        const double* d_vals) {
+    if (!op) return DZ_ERR;
+    if (op->key_kind != DZ_KEY_INT64 || op->no_group) {
+        op->err = "push_device_i64 requires key_kind DZ_KEY_INT64";
+        return DZ_ERR;
+    }
+    if (!op->dict_i64.empty()) {
+        op->err = "cannot mix host int64 pushes and device i64 pushes on one "
+                  "operator (two dictionaries would assign conflicting ids)";
+        return DZ_ERR;
+    }
+    if ((uintptr_t)d_keys & 7) {
+        op->err = "push_device_i64: d_keys must be 8-byte aligned";
+        return DZ_ERR;
+    }
+    CHK(op, hipSetDevice(op->device));
+    if (n_rows <= 0) return process_pending(op);
+    int C = (int)std::min<int64_t>(512,
+                                   std::max<int64_t>(1, (n_rows + 8191) / 8192));
+    if (op->pend.active &&
+        (C > op->C_cap || (op->slide_ms == 0 && n_rows > op->rec_cap))) {
+        if (process_pending(op) != DZ_OK) return DZ_ERR;
+    }
+    if (ensure_intern_i64(op, n_rows) != DZ_OK) return DZ_ERR;
+    dz_window_op::Pend prev = op->pend;
+    op->pend.active = false;
+    /* the output ring buffer is gated like the utf8 push's */
+    int b = op->next_buf;
+    if (op->consumed_valid[b])
+        CHK(op, hipStreamWaitEvent(op->i_stream, op->ev_consumed[b], 0));
+    if (++op->i_seq == 0) op->i_seq = 1; /* 0 is the counter's initial value */
+    timed_on(op, op->i_stream, "intern_i64", (double)n_rows * 12, [&] {
+        dz::launch_intern_i64(op->i_stream, d_keys, n_rows, op->d_i64tab,
+                              op->i_pmask, op->d_ikeys, op->d_ictrs,
+                              op->i_idcap, op->d_ikid[b], op->i_seq,
+                              op->i_fpmask, op->d_dbg);
     });
     if (stage_core(op, n_rows, d_ts_ms, op->d_ikid[b], d_vals, nullptr,
                    /*keys_are_dense=*/true, /*deferred=*/true,
@@ -2550,6 +2658,12 @@ extern "C" dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch) 
         }
         op->n_keys = (int64_t)op->dict_strs.size();
     } else if (op->key_kind == DZ_KEY_INT64) {
+        if (op->d_i64tab) {
+            op->err = "cannot mix host int64 pushes and device i64 pushes on "
+                      "one operator (two dictionaries would assign "
+                      "conflicting ids)";
+            return DZ_ERR;
+        }
         const int64_t* kv = (const int64_t*)kc.data;
         for (int64_t i = 0; i < n; i++) {
             auto it = op->dict_i64.find(kv[i]);

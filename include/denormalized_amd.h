@@ -198,6 +198,23 @@ dz_status dz_window_op_push_device_utf8(dz_window_op* op, int64_t n_rows,
                                         const char* d_key_data,
                                         const double* d_vals);
 
+/* Device-resident push with ARBITRARY INT64 KEYS (sparse ids, hashes,
+ * negative ids): the keys are interned ON DEVICE into dense ids, inside the
+ * measured path, and emitted as the original int64 values. Groups exactly as
+ * dz_window_op_push does on a DZ_KEY_INT64 op: every value from INT64_MIN to
+ * INT64_MAX is a legal key, none is reserved. Borrowed semantics: the
+ * ts/keys/vals buffers stay valid and unmodified until the NEXT call into
+ * the op. Requires key_kind DZ_KEY_INT64 and an 8-byte-aligned d_keys; an op
+ * takes either host pushes or device i64 pushes, never both. Key capacity is
+ * sized from n_keys_hint at create (table: the power of two >= 4x hint, at
+ * least 65,536 slots; distinct keys: half the table) and growth past it
+ * fails loudly — dz_window_op_finish and dz_window_op_kernel_stats return
+ * DZ_ERR — so size the hint for the stream's cardinality. */
+dz_status dz_window_op_push_device_i64(dz_window_op* op, int64_t n_rows,
+                                       const int64_t* d_ts_ms,
+                                       const int64_t* d_keys,
+                                       const double* d_vals);
+
 /* Retrieve emitted closed windows (the stream's output RecordBatch,
  * trigger_windows :220-253). *out = NULL when nothing is pending.
  * The returned batch stays valid until the next poll/destroy. */
@@ -431,7 +448,10 @@ int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count, double m2,
  * nothing. Legal only before the operator's first device utf8 push; results
  * are unaffected at any setting (verification stays byte-exact), except
  * that two NEW colliding keys inside one batch fail at finish as documented
- * for full 64-bit collisions. */
+ * for full 64-bit collisions.
+ * On a DZ_KEY_INT64 op (before its first device i64 push) the mask applies
+ * to the key's hash before the home slot is taken, so small `bits` forces
+ * long probe chains; the key compare stays exact and nothing can fail. */
 dz_status dz_debug_intern_fp_bits(dz_window_op* op, int32_t bits);
 
 const char* dz_version(void);
