@@ -40,19 +40,35 @@ class DataStream:
     def window(self, group_cols, aggs, length_ms, slide_ms=None):
         """datastream.rs:178-196 (StreamingLogicalPlanBuilder::streaming_window,
         logical_plan/mod.rs:27-60). group_cols: [key column name]; aggs:
-        [(op_name, value_col_name), ...]."""
+        [(op_name, value_col_name), ...] or (op_name, value_col_name, alias).
+        Up to 4 distinct value columns (the reference aggregates several
+        columns in one window, examples/examples/kafka_rideshare.rs:73-75);
+        the result column is named by the alias, else by the op name."""
         if len(group_cols) > 1:
             raise ValueError("hot-path shape: at most one group column")
         if self._window is not None:
             raise ValueError("window() already applied")
-        vcols = {c for _, c in aggs}
-        if len(vcols) != 1:
-            raise ValueError("hot-path shape: one aggregate input column")
+        aggs = [tuple(a) for a in aggs]
+        if not aggs or any(len(a) not in (2, 3) for a in aggs):
+            raise ValueError("aggs entries are (op, col) or (op, col, alias)")
+        vcols = []  # distinct value columns, first-appearance order
+        for a in aggs:
+            if a[1] not in vcols:
+                vcols.append(a[1])
+        if len(vcols) > 4:
+            raise ValueError("at most 4 distinct aggregate input columns")
+        names = [a[2] if len(a) == 3 else a[0] for a in aggs]
+        if len(vcols) > 1 or any(len(a) == 3 for a in aggs):
+            dup = sorted({x for x in names if names.count(x) > 1})
+            if dup:
+                raise ValueError(f"result column names collide: {dup} "
+                                 f"(give each aggregate an alias)")
         ds = self._copy()
         ds._window = {
             "group_col": group_cols[0] if group_cols else None,
-            "aggs": list(aggs),
-            "value_col": vcols.pop(),
+            "aggs": aggs,
+            "names": names,
+            "value_cols": vcols,
             "length_ms": int(length_ms),
             "slide_ms": int(slide_ms) if slide_ms else 0,
         }
@@ -76,13 +92,21 @@ class DataStream:
         w = self._window
         if w is None:
             raise ValueError("no window() in pipeline (hot path is window+filter)")
+        no_group = w["group_col"] is None
+        if len(w["value_cols"]) == 1 and all(len(a) == 2 for a in w["aggs"]):
+            aggs = [(a[0], 0) for a in w["aggs"]]
+        else:
+            # batch layout: ts, [key,] then the distinct value columns
+            first = 1 if no_group else 2
+            aggs = [(a[0], first + w["value_cols"].index(a[1]), nm)
+                    for a, nm in zip(w["aggs"], w["names"])]
         op = WindowOp(length_ms=w["length_ms"], slide_ms=w["slide_ms"],
-                      aggs=[(name, 0) for name, _ in w["aggs"]],
+                      aggs=aggs,
                       key_kind=self._key_kind, device=self._ctx.device,
                       n_keys_hint=n_keys_hint,
-                      no_group=w["group_col"] is None)
+                      no_group=no_group)
         for (col, cmp, lit) in self._filters:
-            names = [name for name, _ in w["aggs"]]
+            names = w["names"]
             if col not in names:
                 raise ValueError(f"filter column {col!r} not in aggregate outputs")
             op.set_filter(col, cmp, lit)
@@ -96,8 +120,14 @@ class DataStream:
         try:
             for b in self._batches:
                 keys = b[w["group_col"]] if w["group_col"] is not None else None
-                op.push(b[self._ts_col], keys, b[w["value_col"]],
-                        b.get("_validity"))
+                vcols = w["value_cols"]
+                if len(vcols) == 1:
+                    # "_validity" stays the one-column spelling
+                    bm = b.get("_validity_" + str(vcols[0]), b.get("_validity"))
+                    op.push(b[self._ts_col], keys, b[vcols[0]], bm)
+                else:
+                    op.push(b[self._ts_col], keys, [b[c] for c in vcols],
+                            [b.get("_validity_" + str(c)) for c in vcols])
                 for out in op.poll_all():
                     yield out
             op.finish()

@@ -112,6 +112,11 @@ def lib():
             pass
         L.dz_window_op_push_device_utf8.argtypes = [p, i64, p, p, p, p]
         L.dz_window_op_push_device_i64.argtypes = [p, i64, p, p, p]
+        try:
+            L.dz_window_op_set_extra_values.argtypes = [
+                p, i64, ctypes.POINTER(p), ctypes.POINTER(p)]
+        except AttributeError:  # older engine build (A/B hook)
+            pass
         L.dz_generate_utf8.argtypes = [ctypes.c_int32, ctypes.c_uint64, i64,
                                        i64, i64, p, p, p]
         L.dz_window_op_poll.argtypes = [p, ctypes.POINTER(ctypes.POINTER(DzOutBatch))]
@@ -192,7 +197,15 @@ def _np_ptr(a):
 
 
 class WindowOp:
-    """Python handle over dz_window_op (one partition's stream)."""
+    """Python handle over dz_window_op (one partition's stream).
+
+    aggs entries are (op, col) or (op, col, alias). With 2-tuples only, the
+    column half is ignored and every aggregate reads value_col. As soon as
+    one entry is a 3-tuple, every entry's col is the batch column index it
+    aggregates and alias (default: the op name) names its result column; up
+    to 4 distinct columns, numbered in order of first appearance. The first
+    is the primary; an aggregate on any other column reports its own mask as
+    res[alias + "_valid"]."""
 
     def __init__(self, length_ms, slide_ms=0, aggs=(("count", 0), ("min", 0),
                  ("max", 0), ("avg", 0)), key_kind=KEY_UTF8, n_keys_hint=1024,
@@ -207,12 +220,21 @@ class WindowOp:
         self._agg_arr = (DzAggDesc * n)()
         self.agg_names = []
         self._var_aggs = []  # indices whose column has its own NULL mask
-        for i, (name, _col) in enumerate(aggs):
+        self._by_col = any(len(a) == 3 for a in aggs)
+        self._dcols = []     # distinct value columns, first-appearance order
+        for i, agg in enumerate(aggs):
+            name, col = agg[0], agg[1]
             self._agg_arr[i].op = AGG_BY_NAME[name] if isinstance(name, str) else name
-            if self._agg_arr[i].op in VAR_AGGS:
+            col = int(col) if self._by_col else value_col
+            if col not in self._dcols:
+                self._dcols.append(col)
+            if self._agg_arr[i].op in VAR_AGGS or col != self._dcols[0]:
                 self._var_aggs.append(i)
-            self._agg_arr[i].input_col = value_col
-            self.agg_names.append(name if isinstance(name, str) else str(name))
+            self._agg_arr[i].input_col = col
+            alias = agg[2] if len(agg) == 3 else name
+            self.agg_names.append(alias if isinstance(alias, str) else str(alias))
+        self.n_value_cols = len(self._dcols)
+        self._ts_col, self._group_col = ts_col, group_col
         d = DzWindowDesc(
             window_type=WINDOW_SLIDING if slide_ms else WINDOW_TUMBLING,
             length_ms=length_ms, slide_ms=slide_ms or 0, ts_col=ts_col,
@@ -232,6 +254,8 @@ class WindowOp:
     def push(self, ts_ms, keys, vals, val_valid_bitmap=None):
         """Host-batch push (the drop-in boundary). keys: np.int64 array, or a
         list of str/bytes for utf8. val_valid_bitmap: LSB-first bitmap bytes."""
+        if self._by_col:
+            return self._push_by_col(ts_ms, keys, vals, val_valid_bitmap)
         ts_ms = np.ascontiguousarray(ts_ms, np.int64)
         vals = np.ascontiguousarray(vals, np.float64)
         n = len(ts_ms)
@@ -273,6 +297,87 @@ class WindowOp:
                            _np_ptr(vals).value if n else None)
         batch = DzBatch(n, 3, ctypes.cast(cols, ctypes.POINTER(DzColumn)))
         self._check(self._L.dz_window_op_push(self._h, ctypes.byref(batch)), "push")
+
+    def _push_by_col(self, ts_ms, keys, vals, bitmaps):
+        """Host push of an op declared with (op, col, alias): the batch has
+        ts at ts_col, keys at group_col and each distinct value column at its
+        own index. vals / bitmaps: sequences in distinct-column order (a
+        single array / bitmap is accepted for a one-column op)."""
+        nv = self.n_value_cols
+        if nv == 1 and not isinstance(vals, (list, tuple)):
+            vals, bitmaps = [vals], [bitmaps]
+        if bitmaps is None:
+            bitmaps = [None] * nv
+        if len(vals) != nv or len(bitmaps) != nv:
+            raise ValueError(f"push needs {nv} value columns (and bitmaps), "
+                             f"in distinct-column order")
+        ts_ms = np.ascontiguousarray(ts_ms, np.int64)
+        n = len(ts_ms)
+        used = [self._ts_col] + self._dcols
+        if not self.no_group:
+            used.append(self._group_col)
+        if len(set(used)) != len(used) or min(used) < 0:
+            raise ValueError("ts, group and value column indices must be "
+                             "distinct and non-negative")
+        ncols = max(used) + 1
+        cols = (DzColumn * ncols)()
+        keep = [ts_ms]
+        cols[self._ts_col] = DzColumn(n, None, None,
+                                      _np_ptr(ts_ms).value if n else None)
+        if self.no_group:
+            pass
+        elif self.key_kind == KEY_UTF8:
+            enc = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+            offs = np.zeros(n + 1, np.int32)
+            np.cumsum([len(k) for k in enc], out=offs[1:])
+            data = b"".join(enc)
+            buf = np.frombuffer(data, np.uint8) if data else np.zeros(1, np.uint8)
+            keep += [offs, buf]
+            cols[self._group_col] = DzColumn(n, None, _np_ptr(offs).value,
+                                             _np_ptr(buf).value)
+        else:
+            karr = np.ascontiguousarray(keys, np.int64)
+            keep.append(karr)
+            cols[self._group_col] = DzColumn(
+                n, None, None, _np_ptr(karr).value if n else None)
+        for c, v, bm in zip(self._dcols, vals, bitmaps):
+            v = np.ascontiguousarray(v, np.float64)
+            if len(v) != n:
+                raise ValueError("value column length differs from ts")
+            keep.append(v)
+            if bm is not None:
+                bm = np.ascontiguousarray(bm, np.uint8)
+                if len(bm) < (n + 7) // 8:
+                    raise ValueError("validity bitmap shorter than the batch")
+                keep.append(bm)
+            cols[c] = DzColumn(n, _np_ptr(bm).value if bm is not None else None,
+                               None, _np_ptr(v).value if n else None)
+        batch = DzBatch(n, ncols, ctypes.cast(cols, ctypes.POINTER(DzColumn)))
+        self._check(self._L.dz_window_op_push(self._h, ctypes.byref(batch)),
+                    "push")
+
+    def set_extra_values(self, n, d_vals_list, d_validity_list=None):
+        """Extra value columns (distinct columns 1.., in order) of the NEXT
+        device push of any kind: device pointers to f64 columns and, per
+        column, an LSB-first validity bitmap or None. Borrowed until the call
+        after that push."""
+        def as_p(x):
+            if x is None:
+                return None
+            return x.value if isinstance(x, ctypes.c_void_p) else int(x)
+        k = len(d_vals_list)
+        va = (ctypes.c_void_p * max(k, 1))(*[as_p(x) for x in d_vals_list])
+        ba = None
+        if d_validity_list is not None:
+            if len(d_validity_list) != k:
+                raise ValueError("one validity entry per extra column")
+            ba = (ctypes.c_void_p * max(k, 1))(
+                *[as_p(x) for x in d_validity_list])
+        if k != self.n_value_cols - 1 and self.n_value_cols > 1:
+            raise ValueError(f"op has {self.n_value_cols - 1} extra columns, "
+                             f"got {k}")
+        self._check(self._L.dz_window_op_set_extra_values(
+            self._h, n, va, ba), "set_extra_values")
 
     def push_device(self, n, d_ts, d_kid32, d_vals, borrowed=False):
         """borrowed=True: zero-copy — the op reads these buffers until the
@@ -346,7 +451,7 @@ class WindowOp:
             res["key"] = mk(ob.key_i64, n, ctypes.c_int64)
         for i, name in enumerate(self.agg_names):
             pt = ob.agg_cols[i]
-            if AGG_BY_NAME.get(name, name) == AGG_COUNT or name == "count":
+            if self._agg_arr[i].op == AGG_COUNT:
                 res[name] = mk(pt, n, ctypes.c_int64)
             else:
                 res[name] = mk(pt, n, ctypes.c_double)
@@ -357,7 +462,8 @@ class WindowOp:
             res["valid"] = np.zeros(0, np.uint8)
         for i in self._var_aggs:
             # variance family: own NULL rule (e.g. var_samp of a one-row
-            # group), reported per aggregate
+            # group); aggregates on an extra value column: that column's
+            # NULLs. Both reported per aggregate
             name = self.agg_names[i]
             pm = ob.agg_valid_cols[i] if n and ob.agg_valid_cols else None
             if pm:

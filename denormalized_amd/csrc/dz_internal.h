@@ -49,6 +49,21 @@ struct FoldChunk {
     int32_t tl_nw;       /* two-level mode: windows per batch (0 = off) */
 };
 
+/* Extra value columns of a multi-column op (distinct input columns 1..nx, in
+ * order of first appearance in aggs), passed to the fold by value: the fold
+ * gathers vals[c][row] (and bit `row` of valid[c], LSB-first; null = all
+ * valid) by the record's batch row index. slab is the extras' persistent
+ * state, [slot][col][{cnt,min,max,sum}][kcap] 8-byte cells (32 B per group
+ * per extra), `cells` its size for the bounds guard. nx == 0: unused. */
+constexpr int MAX_EXTRA_COLS = 3;
+struct FoldExtras {
+    const double* vals[MAX_EXTRA_COLS] = {};
+    const uint8_t* valid[MAX_EXTRA_COLS] = {};
+    uint64_t* slab = nullptr;
+    int64_t cells = 0;
+    int32_t nx = 0;
+};
+
 /* Launch wrappers implemented in kernels.hip. All run on `stream`;
  * n = rows in batch, C = partition chunks (hist/scatter grid). */
 void launch_gen(hipStream_t stream, uint64_t seed, int64_t t0, int64_t start_row,
@@ -121,7 +136,8 @@ void launch_regroup_fold(hipStream_t stream, const uint4* d_grec,
                          const FoldChunk& fc, const int32_t* d_slot_of_widx,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
-                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells);
+                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells,
+                         const FoldExtras& fx);
 
 void launch_regroup_l1(hipStream_t stream, const uint4* d_grec,
                        const uint32_t* d_bucket_base,
@@ -136,7 +152,7 @@ void launch_regroup_l2_fold(hipStream_t stream, const uint4* d_grec2,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
                             uint32_t* d_dbg, double* v_base,
-                            int64_t vslab_cells);
+                            int64_t vslab_cells, const FoldExtras& fx);
 
 struct EGatherSlots {
     int32_t s[16];
@@ -266,6 +282,10 @@ constexpr int EMIT_RBINS = 2048;
 void launch_reset_slots(hipStream_t stream, const int32_t* d_slots, int ns,
                         int64_t kcap, uint64_t* s_cnt, uint64_t* s_first);
 
+/* multi-column ops: zero every extra's cnt of the same slots */
+void launch_reset_slots_x(hipStream_t stream, const int32_t* d_slots, int ns,
+                          int nx, int64_t kcap, uint64_t* x_slab);
+
 /* host-path emission: pack up to 16 closing window slots' state slabs into
  * one contiguous staging area (one launch + ONE big D2H replaces a per-close
  * copy on the push thread; slot ids travel by value in the kernel args) */
@@ -277,6 +297,11 @@ void launch_egather_slabs(hipStream_t stream, const uint64_t* s_base,
 void launch_egather_slabs_var(hipStream_t stream, const uint64_t* s_base,
                               const double* v_base, int64_t kcap,
                               EGatherSlots slots, int gcount, uint64_t* out);
+/* multi-column ops: (5 + 4 nx) * kcap cells per close — the 5-field slab,
+ * then the slot's extras from the side slab */
+void launch_egather_slabs_x(hipStream_t stream, const uint64_t* s_base,
+                            const uint64_t* x_slab, int nx, int64_t kcap,
+                            EGatherSlots slots, int gcount, uint64_t* out);
 void launch_arm_scalars(hipStream_t stream, uint64_t* scalars);
 
 void launch_fill_i64(hipStream_t stream, int64_t* d_p, int64_t n, int64_t v);

@@ -1059,17 +1059,42 @@ __device__ __forceinline__ void welford_step(double v, uint64_t n,
 
 /* VAR: the fold also carries the variance family's (mean, m2) accumulators,
  * persisted in the side slab v_base ([slot][{mean,m2}][kcap] f64). VAR=false
- * compiles to the kernels without them (v_base/vslab_cells unused). */
-template <int MODE, bool VAR = false>
+ * compiles to the kernels without them (v_base/vslab_cells unused).
+ * NX: extra value columns (0..3) of a multi-column op. The fold gathers each
+ * extra's value (and validity bit) by the record's batch row index and keeps
+ * {cnt, min, max, sum} per extra in registers, persisted in the side slab
+ * fx.slab ([slot][col][{cnt,min,max,sum}][kcap], same (slot, kloc, bucket)
+ * cell as the main slab, bounds-guarded through dbg[1]). The FoldExtras
+ * argument exists only when NX > 0 (the trailing pack is empty otherwise), so
+ * the NX=0 kernels keep their argument block and compile to the code they
+ * were before extras existed. */
+__device__ __forceinline__ const FoldExtras& pick_fx(const FoldExtras& f) {
+    return f;
+}
+/* per-extra register accumulators; no members at all when NX == 0 */
+template <int N>
+struct XAcc {
+    uint64_t cnt[N];
+    double mn[N], mx[N], sm[N];
+};
+template <>
+struct XAcc<0> {};
+
+template <int MODE, bool VAR = false, int NX = 0, typename... XA>
 __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
         const uint32_t* bucket_base, FoldChunk fc,
         const uint32_t* b1offs, const uint32_t* b1lens, uint32_t* binoffs,
         uint32_t* binlens, uint4* orec,
         const int32_t* slot_of_widx, uint64_t* s_cnt, double* s_min,
         double* s_max, double* s_sum, uint64_t* s_first, int64_t slab_cells,
-        uint32_t* dbg, double* v_base, int64_t vslab_cells) {
+        uint32_t* dbg, double* v_base, int64_t vslab_cells, XA... xa) {
+    static_assert(sizeof...(XA) == (NX > 0 ? 1 : 0),
+                  "FoldExtras is passed exactly when NX > 0");
     static_assert(!VAR || MODE == RG_DIRECT_FOLD || MODE == RG_L2_FOLD,
                   "only the fold modes carry variance state");
+    static_assert(NX >= 0 && NX <= MAX_EXTRA_COLS &&
+                  (NX == 0 || (!VAR && MODE != RG_L1)),
+                  "extras ride the fold modes, without variance state");
     constexpr bool FOLD = (MODE == RG_DIRECT_FOLD || MODE == RG_L2_FOLD);
     __shared__ uint32_t cnt[GCAP];    /* whole-segment bin counts (L1) */
     __shared__ uint32_t gcur[GCAP];   /* segment-region bin cursors (L1) */
@@ -1128,6 +1153,15 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     double f_mn = 0.0, f_mx = 0.0, f_sm = 0.0;
     int64_t f_vidx = 0;               /* VAR: side-slab cell of `mean` */
     double f_mean = 0.0, f_m2 = 0.0;  /* VAR: Welford state */
+    [[maybe_unused]] int64_t f_xidx = 0; /* NX: side-slab cell of extra 0's cnt */
+    [[maybe_unused]] XAcc<NX> x;         /* NX: per-extra accumulators */
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int c = 0; c < NX; c++) {
+            x.cnt[c] = 0;
+            x.mn[c] = x.mx[c] = x.sm[c] = 0.0;
+        }
+    }
     if (FOLD) {
         const int g = threadIdx.x;
         int my_widx = 0, my_kloc = 0;
@@ -1155,6 +1189,18 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                          (((int64_t)my_kloc << LOG_NB) | bkt);
                 if (slot < 0 || f_vidx < 0 ||
                     f_vidx + fc.kcap >= vslab_cells) {
+                    dbg[1] = 1;
+                    f_own = false;
+                }
+            }
+            if constexpr (NX > 0) {
+                const FoldExtras& fx = pick_fx(xa...);
+                /* same cell, 4 fields per extra: field f of extra c sits
+                 * (4 * c + f) * kcap cells after f_xidx */
+                f_xidx = slot * ((int64_t)(4 * NX) * fc.kcap) +
+                         (((int64_t)my_kloc << LOG_NB) | bkt);
+                if (slot < 0 || f_xidx < 0 ||
+                    f_xidx + (int64_t)(4 * NX - 1) * fc.kcap >= fx.cells) {
                     dbg[1] = 1;
                     f_own = false;
                 }
@@ -1291,6 +1337,25 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                             f_m2 = v_base[f_vidx + fc.kcap];
                         }
                     }
+                    if constexpr (NX > 0) {
+                        const FoldExtras& fx = pick_fx(xa...);
+#pragma unroll
+                        for (int c = 0; c < NX; c++) {
+                            /* each extra has its own cnt: min/max/sum are
+                             * read only behind it, so whatever a recycled
+                             * slot still holds never surfaces */
+                            const int64_t xi = f_xidx + (int64_t)(4 * c) * fc.kcap;
+                            x.cnt[c] = fx.slab[xi];
+                            if (x.cnt[c] > 0) {
+                                x.mn[c] = __longlong_as_double(
+                                    (long long)fx.slab[xi + fc.kcap]);
+                                x.mx[c] = __longlong_as_double(
+                                    (long long)fx.slab[xi + 2 * fc.kcap]);
+                                x.sm[c] = __longlong_as_double(
+                                    (long long)fx.slab[xi + 3 * fc.kcap]);
+                            }
+                        }
+                    }
                 }
                 if (f_fst == ~0ULL)
                     f_fst = fc.row_base + (s_rec[seg0].z & 0x7FFFFFFFu);
@@ -1305,6 +1370,24 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                         f_sm += v;
                         f_cnt++;
                         if (VAR) welford_step(v, f_cnt, f_mean, f_m2);
+                    }
+                    if constexpr (NX > 0) {
+                        const FoldExtras& fx = pick_fx(xa...);
+                        /* extras: gathered by batch row index, each under
+                         * its own validity bit, whatever the primary's is */
+                        const uint32_t row = rec.z & 0x7FFFFFFFu;
+#pragma unroll
+                        for (int c = 0; c < NX; c++) {
+                            const uint8_t* bm = fx.valid[c];
+                            if (!bm || ((bm[row >> 3] >> (row & 7)) & 1)) {
+                                const double xv = fx.vals[c][row];
+                                const bool xfresh = x.cnt[c] == 0;
+                                x.mn[c] = (xfresh || xv < x.mn[c]) ? xv : x.mn[c];
+                                x.mx[c] = (xfresh || xv > x.mx[c]) ? xv : x.mx[c];
+                                x.sm[c] += xv;
+                                x.cnt[c]++;
+                            }
+                        }
                     }
                 }
             }
@@ -1333,7 +1416,43 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
             v_base[f_vidx] = f_mean;
             v_base[f_vidx + fc.kcap] = f_m2;
         }
+        if constexpr (NX > 0) {
+            const FoldExtras& fx = pick_fx(xa...);
+#pragma unroll
+            for (int c = 0; c < NX; c++) {
+                const int64_t xi = f_xidx + (int64_t)(4 * c) * fc.kcap;
+                fx.slab[xi] = x.cnt[c];
+                fx.slab[xi + fc.kcap] =
+                    (uint64_t)__double_as_longlong(x.mn[c]);
+                fx.slab[xi + 2 * fc.kcap] =
+                    (uint64_t)__double_as_longlong(x.mx[c]);
+                fx.slab[xi + 3 * fc.kcap] =
+                    (uint64_t)__double_as_longlong(x.sm[c]);
+            }
+        }
     }
+}
+
+/* the fold-mode launch: picks the instantiation from the variance slab and
+ * the number of extra value columns (never both: create refuses that) */
+template <int MODE, typename... A>
+static void launch_fold_mode(dim3 grid, hipStream_t s, double* v_base,
+                             const FoldExtras& fx, A... a) {
+    if (v_base)
+        hipLaunchKernelGGL((k_regroup_t<MODE, true, 0>), grid, dim3(BLOCK), 0,
+                           s, a...);
+    else if (fx.nx == 1)
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 1, FoldExtras>), grid,
+                           dim3(BLOCK), 0, s, a..., fx);
+    else if (fx.nx == 2)
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 2, FoldExtras>), grid,
+                           dim3(BLOCK), 0, s, a..., fx);
+    else if (fx.nx == 3)
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 3, FoldExtras>), grid,
+                           dim3(BLOCK), 0, s, a..., fx);
+    else
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 0>), grid, dim3(BLOCK), 0,
+                           s, a...);
 }
 
 void launch_regroup_fold(hipStream_t s, const uint4* d_grec,
@@ -1341,19 +1460,14 @@ void launch_regroup_fold(hipStream_t s, const uint4* d_grec,
                          const FoldChunk& fc, const int32_t* d_slot_of_widx,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
-                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells) {
-    if (v_base)
-        hipLaunchKernelGGL((k_regroup_t<RG_DIRECT_FOLD, true>), dim3(NB),
-                           dim3(BLOCK), 0, s, d_grec, d_bucket_base, fc,
-                           nullptr, nullptr, nullptr, nullptr, nullptr,
-                           d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first,
-                           slab_cells, d_dbg, v_base, vslab_cells);
-    else
-    hipLaunchKernelGGL(k_regroup_t<RG_DIRECT_FOLD>, dim3(NB), dim3(BLOCK), 0, s,
-                       d_grec, d_bucket_base, fc, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, d_slot_of_widx,
-                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg,
-                       nullptr, 0);
+                         uint32_t* d_dbg, double* v_base, int64_t vslab_cells,
+                         const FoldExtras& fx) {
+    launch_fold_mode<RG_DIRECT_FOLD>(
+        dim3(NB), s, v_base, fx, d_grec, d_bucket_base, fc,
+        (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+        (uint32_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr,
+        d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first, slab_cells,
+        d_dbg, v_base, v_base ? vslab_cells : (int64_t)0);
 }
 
 void launch_regroup_l1(hipStream_t s, const uint4* d_grec,
@@ -1373,19 +1487,12 @@ void launch_regroup_l2_fold(hipStream_t s, const uint4* d_grec2,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
                             uint32_t* d_dbg, double* v_base,
-                            int64_t vslab_cells) {
-    if (v_base)
-        hipLaunchKernelGGL((k_regroup_t<RG_L2_FOLD, true>), dim3(NB, nb1),
-                           dim3(BLOCK), 0, s, d_grec2, d_bucket_base, fc,
-                           d_b1offs, d_b1lens, nullptr, nullptr, nullptr,
-                           d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first,
-                           slab_cells, d_dbg, v_base, vslab_cells);
-    else
-    hipLaunchKernelGGL(k_regroup_t<RG_L2_FOLD>, dim3(NB, nb1), dim3(BLOCK), 0, s,
-                       d_grec2, d_bucket_base, fc, d_b1offs, d_b1lens,
-                       nullptr, nullptr, nullptr, d_slot_of_widx,
-                       s_cnt, s_min, s_max, s_sum, s_first, slab_cells, d_dbg,
-                       nullptr, 0);
+                            int64_t vslab_cells, const FoldExtras& fx) {
+    launch_fold_mode<RG_L2_FOLD>(
+        dim3(NB, nb1), s, v_base, fx, d_grec2, d_bucket_base, fc, d_b1offs,
+        d_b1lens, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr,
+        d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first, slab_cells,
+        d_dbg, v_base, v_base ? vslab_cells : (int64_t)0);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1762,6 +1869,30 @@ void launch_reset_slots(hipStream_t s, const int32_t* d_slots, int ns,
                        ns, kcap, s_cnt, s_first);
 }
 
+/* multi-column ops: zero every extra's cnt of the same slots (min/max/sum
+ * may stay stale: the fold reads them only behind a non-zero cnt) */
+__global__ void k_reset_slots_x(const int32_t* slots, int ns, int nx,
+                                int64_t kcap, uint64_t* x_slab) {
+    const int64_t per_slot = (int64_t)nx * kcap;
+    const int64_t total = (int64_t)ns * per_slot;
+    const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+         i += gstride) {
+        const int64_t si = i / per_slot, rem = i % per_slot;
+        const int64_t c = rem / kcap, k = rem % kcap;
+        x_slab[slots[si] * (4 * per_slot) + c * 4 * kcap + k] = 0;
+    }
+}
+
+void launch_reset_slots_x(hipStream_t s, const int32_t* d_slots, int ns,
+                          int nx, int64_t kcap, uint64_t* x_slab) {
+    int64_t total = (int64_t)ns * nx * kcap;
+    int blocks = (int)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 2048);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_reset_slots_x, dim3(blocks), dim3(BLOCK), 0, s,
+                       d_slots, ns, nx, kcap, x_slab);
+}
+
 } // namespace dz
 
 /* ------------------------------------------------------------------ */
@@ -1815,6 +1946,34 @@ void dz::launch_egather_slabs_var(hipStream_t s, const uint64_t* s_base,
     dim3 grid(bx, gcount);
     hipLaunchKernelGGL(k_egather_slabs_var, grid, dim3(dz::BLOCK), 0, s,
                        s_base, (const uint64_t*)v_base, kcap, slots, out);
+}
+
+/* multi-column ops: each packed close is the 5-field slab followed by the
+ * slot's 4 * nx extra fields from the side slab ((5 + 4 nx) * kcap cells) */
+__global__ void k_egather_slabs_x(const uint64_t* __restrict__ s_base,
+                                  const uint64_t* __restrict__ x_slab, int nx,
+                                  int64_t kcap, dz::EGatherSlots slots,
+                                  uint64_t* __restrict__ out) {
+    const int g = blockIdx.y;
+    const int64_t slot = slots.s[g];
+    const int64_t ncell = (int64_t)(5 + 4 * nx) * kcap;
+    const uint64_t* src = s_base + slot * (5 * kcap);
+    const uint64_t* xs = x_slab + slot * ((int64_t)(4 * nx) * kcap);
+    uint64_t* dst = out + (int64_t)g * ncell;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < ncell; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = i < 5 * kcap ? src[i] : xs[i - 5 * kcap];
+}
+
+void dz::launch_egather_slabs_x(hipStream_t s, const uint64_t* s_base,
+                                const uint64_t* x_slab, int nx, int64_t kcap,
+                                dz::EGatherSlots slots, int gcount,
+                                uint64_t* out) {
+    int bx = (int)std::min<int64_t>(
+        ((int64_t)(5 + 4 * nx) * kcap + dz::BLOCK - 1) / dz::BLOCK, 512);
+    dim3 grid(bx, gcount);
+    hipLaunchKernelGGL(k_egather_slabs_x, grid, dim3(dz::BLOCK), 0, s, s_base,
+                       x_slab, nx, kcap, slots, out);
 }
 
 /* arm the per-push scalar block (min=+inf pattern, max/kid=0) in ONE tiny

@@ -64,6 +64,9 @@ extern "C" int64_t dz_debug_windows_for_range(int64_t min_ts, int64_t max_ts,
     return n;
 }
 
+static_assert(DZ_MAX_VALUE_COLS == 1 + dz::MAX_EXTRA_COLS,
+              "the fold carries the primary plus MAX_EXTRA_COLS extras");
+
 static inline bool is_var_op(int32_t o) {
     return o >= DZ_AGG_VAR_SAMP && o <= DZ_AGG_STDDEV_POP;
 }
@@ -234,6 +237,33 @@ struct dz_window_op {
      * column of the packed slab; finalisation is host-side). */
     bool has_var = false;
     double* v_base = nullptr;
+    /* several value columns: the distinct input columns in order of first
+     * appearance in aggs. Column 0 is the primary and rides the records and
+     * the main slab exactly as on a single-column op; columns 1..nx are the
+     * extras, gathered by row index in the fold and kept in the side slab
+     * x_slab, [slot][col][{cnt,min,max,sum}][kcap] — allocated only when
+     * nx > 0. k_reset_slots_x zeroes every extra's cnt on slot reuse. Such
+     * ops emit through the host-built path at every key count (the extras
+     * travel as 4 * nx more columns of the packed slab). */
+    int32_t nx = 0;
+    int32_t dcols[1 + dz::MAX_EXTRA_COLS] = {}; /* batch column index */
+    std::vector<int32_t> agg_col;  /* per aggregate: 0 primary, 1..nx extra */
+    uint64_t* x_slab = nullptr;
+    /* 8-byte cells of one packed close in the pinned group buffers */
+    int64_t close_fields() const { return has_var ? 6 : 5 + 4 * nx; }
+    bool host_route() const { return has_var || nx > 0; }
+    struct XCols { /* one push's extra columns (device pointers) */
+        const double* vals[dz::MAX_EXTRA_COLS] = {};
+        const uint8_t* valid[dz::MAX_EXTRA_COLS] = {};
+    };
+    /* dz_window_op_set_extra_values: borrowed, consumed by the next device
+     * push */
+    bool x_att_on = false;
+    int64_t x_att_n = 0;
+    XCols x_att;
+    /* host-batch path: op-owned device copies of the extras */
+    double* d_xvals[dz::MAX_EXTRA_COLS] = {};
+    uint8_t* d_xbm[dz::MAX_EXTRA_COLS] = {};
     struct FreeSlot {
         int32_t slot;
         hipEvent_t ev;     /* copy-done gate or null */
@@ -328,6 +358,7 @@ struct dz_window_op {
         const int32_t* kid = nullptr;
         const double* vals = nullptr;
         const uint8_t* valbm = nullptr;
+        XCols x; /* multi-column ops: the extras of this batch */
     } pend;
     int next_buf = 0;
     int64_t* d_sts[2] = {};   /* op-owned device input ring (device-push) */
@@ -624,6 +655,23 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
                                        span * 8, hipMemcpyDeviceToDevice, op->stream));
         }
     }
+    uint64_t* n_xslab = nullptr;
+    if (op->nx > 0) {
+        /* the extras' side slab regrows with the main slab: every cnt zero,
+         * open slots copied field by field */
+        const int nf = 4 * op->nx;
+        size_t xstride_new = (size_t)kcap_new * nf, xstride_old = (size_t)op->kcap * nf;
+        CHK(op, hipMalloc(&n_xslab, xstride_new * nslots_new * 8));
+        CHK(op, hipMemsetAsync(n_xslab, 0, xstride_new * nslots_new * 8, op->stream));
+        for (auto& kv : op->open) {
+            int32_t s = kv.second.slot;
+            int64_t span = std::min(op->kcap, kcap_new);
+            for (int f = 0; f < nf; f++)
+                CHK(op, hipMemcpyAsync(n_xslab + s * xstride_new + (size_t)f * kcap_new,
+                                       op->x_slab + s * xstride_old + (size_t)f * op->kcap,
+                                       span * 8, hipMemcpyDeviceToDevice, op->stream));
+        }
+    }
     CHK(op, hipStreamSynchronize(op->stream));
     for (int s = 0; s < dz_window_op::E_CSTREAMS; s++) /* emission reads s_base */
         if (op->c_streams[s])
@@ -631,6 +679,10 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
     if (op->has_var) {
         hipFree(op->v_base);
         op->v_base = n_vbase;
+    }
+    if (op->nx > 0) {
+        hipFree(op->x_slab);
+        op->x_slab = n_xslab;
     }
     hipFree(op->s_base);
     op->s_base = n_base;
@@ -667,6 +719,29 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
         }
         any_var = any_var || is_var_op(o);
     }
+    /* distinct input columns, numbered in order of first appearance */
+    int32_t dcols[1 + dz::MAX_EXTRA_COLS];
+    int32_t ndc = 0;
+    std::vector<int32_t> agg_col(desc->n_aggs);
+    for (int32_t a = 0; a < desc->n_aggs; a++) {
+        int32_t c = 0;
+        while (c < ndc && dcols[c] != desc->aggs[a].input_col) c++;
+        if (c == ndc) {
+            if (ndc == 1 + dz::MAX_EXTRA_COLS) {
+                g_err = "aggregates read more than " +
+                        std::to_string(1 + dz::MAX_EXTRA_COLS) +
+                        " distinct input columns (DZ_MAX_VALUE_COLS)";
+                return nullptr;
+            }
+            dcols[ndc++] = desc->aggs[a].input_col;
+        }
+        agg_col[a] = c;
+    }
+    if (any_var && ndc > 1) {
+        g_err = "variance-family aggregates need a single input column "
+                "(several value columns are not supported with them)";
+        return nullptr;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= desc->device) {
         g_err = "no HIP device available (this operator has no CPU fallback)";
@@ -682,6 +757,9 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
     op->key_kind = op->no_group ? DZ_KEY_DENSE_INT64 : desc->key_kind;
     op->aggs.assign(desc->aggs, desc->aggs + desc->n_aggs);
     op->has_var = any_var;
+    op->nx = ndc - 1;
+    memcpy(op->dcols, dcols, sizeof(dcols[0]) * ndc);
+    op->agg_col = agg_col;
     op->device = desc->device;
     op->max_open = desc->max_open_windows > 0 ? desc->max_open_windows : 4096;
     bool cs_ok = true;
@@ -778,6 +856,11 @@ extern "C" void dz_window_op_destroy(dz_window_op* op) {
     }
     hipFree(op->s_base);
     hipFree(op->v_base);
+    hipFree(op->x_slab);
+    for (int c = 0; c < dz::MAX_EXTRA_COLS; c++) {
+        hipFree(op->d_xvals[c]);
+        hipFree(op->d_xbm[c]);
+    }
     hipFree(op->d_ghist[0]); hipFree(op->d_ghist[1]);
     hipFree(op->d_gofs[0]); hipFree(op->d_gofs[1]);
     hipFree(op->d_total[0]); hipFree(op->d_total[1]);
@@ -902,6 +985,19 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const double* f_sum = (const double*)(slab + 4 * kcap);
     const double* f_m2 =
         op->has_var ? (const double*)(slab + 5 * kcap) : nullptr;
+    /* multi-column ops: column c's (cnt, min, max, sum) — the main slab's for
+     * the primary, fields 5 + 4 (c - 1) .. of the packed close for extra c */
+    const uint64_t* c_cnt[1 + dz::MAX_EXTRA_COLS] = {f_cnt};
+    const double* c_min[1 + dz::MAX_EXTRA_COLS] = {f_min};
+    const double* c_max[1 + dz::MAX_EXTRA_COLS] = {f_max};
+    const double* c_sum[1 + dz::MAX_EXTRA_COLS] = {f_sum};
+    for (int c = 1; c <= op->nx; c++) {
+        const uint64_t* x = slab + (int64_t)(5 + 4 * (c - 1)) * kcap;
+        c_cnt[c] = x;
+        c_min[c] = (const double*)(x + kcap);
+        c_max[c] = (const double*)(x + 2 * kcap);
+        c_sum[c] = (const double*)(x + 3 * kcap);
+    }
 
     /* groups in first-seen (insertion) order: GroupValues emits insertion
      * order; sort touched keys by first-row sequence (first values are
@@ -931,10 +1027,11 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     /* filter pushdown (datastream.rs:94-105) — keep list */
     std::vector<int32_t> rows;
     rows.reserve(touched.size());
+    const int fc = op->agg_col[op->f_idx]; /* the filtered aggregate's column */
     for (auto& p : touched) {
         int32_t k = p.second;
-        if (filter_pass(op, f_cnt[k], f_min[k], f_max[k], f_sum[k],
-                        f_m2 ? f_m2[k] : 0.0))
+        if (filter_pass(op, c_cnt[fc][k], c_min[fc][k], c_max[fc][k],
+                        c_sum[fc][k], f_m2 ? f_m2[k] : 0.0))
             rows.push_back(k);
     }
     size_t n = rows.size(), na = op->aggs.size();
@@ -942,9 +1039,23 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     OutBuf& ob = *out;
     ob.agg_i64.resize(na);
     ob.agg_f64.resize(na);
-    if (op->has_var) ob.agg_valid_a.resize(na);
+    if (op->has_var || op->nx > 0) ob.agg_valid_a.resize(na);
     build_keys(op, rows.data(), n, ob, false);
     for (size_t a = 0; a < na; a++) {
+        /* each aggregate reads its own column's accumulators */
+        const uint64_t* f_cnt = c_cnt[op->agg_col[a]];
+        const double* f_min = c_min[op->agg_col[a]];
+        const double* f_max = c_max[op->agg_col[a]];
+        const double* f_sum = c_sum[op->agg_col[a]];
+        if (op->agg_col[a] > 0) {
+            /* extra-column aggregates carry their own mask: NULL while the
+             * column has no valid row in the group; count is never NULL */
+            auto& msk = ob.agg_valid_a[a];
+            msk.resize(n);
+            const bool is_count = op->aggs[a].op == DZ_AGG_COUNT;
+            for (size_t i = 0; i < n; i++)
+                msk[i] = (is_count || f_cnt[rows[i]] > 0) ? 1 : 0;
+        }
         switch (op->aggs[a].op) {
             case DZ_AGG_COUNT: {
                 auto& col = ob.agg_i64[a];
@@ -1244,7 +1355,7 @@ static void emit_worker_main(dz_window_op* op) {
              * close's slab directly into the pinned group buffer */
             const uint64_t* slab = job.gbuf >= 0
                 ? op->e_gbufs[job.gbuf] +
-                      (size_t)job.goff * job.kcap * (op->has_var ? 6 : 5)
+                      (size_t)job.goff * job.kcap * op->close_fields()
                 : op->e_slabs[job.slab];
             build_emission_host(op, job.wstart, job.wend, job.n_keys, job.kcap,
                                 slab, &ob);
@@ -1351,16 +1462,18 @@ static dz_status ensure_emission(dz_window_op* op) {
                 hipHostFree(op->e_gbufs[i]);
                 op->e_gbufs[i] = nullptr;
             }
-        /* variance-declaring ops emit host-built at EVERY key count, so
-         * their group buffers exist at every kcap: as many whole 6-column
-         * closes as fit a 64 MiB budget (at least one, at most EGROUP) */
-        bool have_gbufs = kc <= 65536 || op->has_var;
+        /* variance-declaring and multi-column ops emit host-built at EVERY
+         * key count, so their group buffers exist at every kcap: as many
+         * whole packed closes (6, or 5 + 4 nx, columns) as fit a 64 MiB
+         * budget (at least one, at most EGROUP) */
+        bool have_gbufs = kc <= 65536 || op->host_route();
         op->e_gbuf_closes = dz_window_op::E_POOL / 2;
-        if (op->has_var)
+        if (op->host_route())
             op->e_gbuf_closes = (int32_t)std::min<int64_t>(
                 dz_window_op::E_POOL / 2,
-                std::max<int64_t>(1, ((int64_t)64 << 20) / (kc * 6 * 8)));
-        op->e_gbuf_cells = (int64_t)op->e_gbuf_closes * kc * (op->has_var ? 6 : 5);
+                std::max<int64_t>(1, ((int64_t)64 << 20) /
+                                         (kc * op->close_fields() * 8)));
+        op->e_gbuf_cells = (int64_t)op->e_gbuf_closes * kc * op->close_fields();
         if (have_gbufs) {
             size_t gbytes = (size_t)op->e_gbuf_cells * 8;
             for (int i = 0; i < dz_window_op::E_GBUFS; i++) {
@@ -1577,17 +1690,23 @@ static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
          * fully asynchronous for the push thread (hipMemcpyAsync D2H
          * was measured performing the transfer at ENQUEUE time) */
         HostTimer htg(op, "h_trig_gather");
-        if (op->has_var) {
-            if ((int64_t)gcount * 6 * op->kcap > op->e_gbuf_cells) {
+        if (op->host_route()) {
+            if ((int64_t)gcount * op->close_fields() * op->kcap >
+                op->e_gbuf_cells) {
                 op->err = "internal: emission group of " +
                           std::to_string(gcount) + " closes x " +
                           std::to_string(op->kcap) +
                           " keys overflows the pinned group buffer";
                 return DZ_ERR;
             }
-            dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
-                                         op->v_base, op->kcap, gs, gcount,
-                                         op->e_gbufs_dev[gbuf]);
+            if (op->has_var)
+                dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
+                                             op->v_base, op->kcap, gs, gcount,
+                                             op->e_gbufs_dev[gbuf]);
+            else
+                dz::launch_egather_slabs_x(op->copy_stream, op->s_base,
+                                           op->x_slab, op->nx, op->kcap, gs,
+                                           gcount, op->e_gbufs_dev[gbuf]);
         } else {
             dz::launch_egather_slabs(op->copy_stream, op->s_base,
                                      op->kcap * 5, gs, gcount,
@@ -1782,7 +1901,7 @@ static dz_status trigger_windows(dz_window_op* op) {
     constexpr size_t EGROUP = dz_window_op::E_POOL / 2;
     /* variance-declaring ops take the host-built path at every key count
      * (the device chains carry no m2 column) */
-    const bool dev_path_g = op->n_keys > 65536 && !op->has_var;
+    const bool dev_path_g = op->n_keys > 65536 && !op->host_route();
     /* small closes (passer hint at or below the threshold) share one
      * group-batched device chain; large ones keep the per-close chain */
     static const uint32_t group_max = [] {
@@ -1796,7 +1915,7 @@ static dz_status trigger_windows(dz_window_op* op) {
     size_t g0 = 0;
     while (g0 < closed.size()) {
         size_t gstep = EGROUP;
-        if (op->has_var)
+        if (op->host_route())
             gstep = std::min<size_t>(gstep,
                                      (size_t)std::max(1, op->e_gbuf_closes));
         if (grouped_ok)
@@ -1809,11 +1928,12 @@ static dz_status trigger_windows(dz_window_op* op) {
             st = enqueue_group_device(op, cl, g1c);
         } else if (!dev_path_g && op->e_gbufs[0]) {
             st = enqueue_group_host(op, cl, g1c);
-        } else if (op->has_var) {
+        } else if (op->host_route()) {
             /* unreachable while ensure_emission holds: the per-close staging
-             * carries no m2 column — refuse rather than emit without it */
-            op->err = "internal: variance aggregates need the pinned group "
-                      "buffers (allocation missing)";
+             * carries no m2 / extra columns — refuse rather than emit
+             * without them */
+            op->err = "internal: variance / multi-column aggregates need the "
+                      "pinned group buffers (allocation missing)";
             st = DZ_ERR;
         } else {
             st = enqueue_per_close(op, cl, g1c, &g1c);
@@ -1873,7 +1993,8 @@ static dz_status ensure_scratch(dz_window_op* op, int C, int64_t nrec) {
 static dz_status stage_core(dz_window_op* op, int64_t n, const int64_t* d_ts,
                             const int32_t* d_kid, const double* d_vals,
                             const uint8_t* d_valbm, bool keys_are_dense,
-                            bool deferred, bool borrow = false) {
+                            bool deferred, bool borrow = false,
+                            const dz_window_op::XCols* xc = nullptr) {
     if (n >= (1LL << 31)) {
         op->err = "batch exceeds 2^31 rows; push smaller batches";
         return DZ_ERR;
@@ -1959,6 +2080,7 @@ static dz_status stage_core(dz_window_op* op, int64_t n, const int64_t* d_ts,
     op->pend.kid = d_kid;
     op->pend.vals = d_vals;
     op->pend.valbm = d_valbm;
+    op->pend.x = xc ? *xc : dz_window_op::XCols();
     if (deferred && !borrow) {
         /* the caller may release its input buffers once we return: wait for
          * the ring copies (typically tens of µs — the ring slot is idle) */
@@ -2084,6 +2206,9 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                                op->stream));
         dz::launch_reset_slots(op->stream, op->d_resetlist, ns, op->kcap,
                                op->s_cnt, op->s_first);
+        if (op->nx > 0)
+            dz::launch_reset_slots_x(op->stream, op->d_resetlist, ns, op->nx,
+                                     op->kcap, op->x_slab);
     }
     if (nw > 0) {
         memcpy(op->h_slotmap[b], slotmap.data(), (size_t)nw * 4);
@@ -2114,6 +2239,16 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
      * ST_RECORDS LDS staging (a 64-row floor overflowed it for window/hop
      * ratios above 32 — found by the randomized deep matrix) */
     int32_t st_rows = (int32_t)std::max<int64_t>(1, dz::ST_RECORDS / expand);
+    dz::FoldExtras fx; /* nx == 0 on single-column ops: the kernels they had */
+    fx.nx = op->nx;
+    if (op->nx > 0) {
+        for (int c = 0; c < op->nx; c++) {
+            fx.vals[c] = P.x.vals[c];
+            fx.valid[c] = P.x.valid[c];
+        }
+        fx.slab = op->x_slab;
+        fx.cells = (int64_t)op->nslots * 4 * op->nx * op->kcap;
+    }
     const int64_t klocs = op->kcap >> dz::LOG_NB;
     const int64_t khigh = (klocs + 255) >> 8;
     /* Window-subrange self-split: when the batch spans so many windows that
@@ -2197,7 +2332,8 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                                            op->s_first,
                                            (int64_t)op->nslots * 5 * op->kcap,
                                            op->d_dbg, op->v_base,
-                                           (int64_t)op->nslots * 2 * op->kcap);
+                                           (int64_t)op->nslots * 2 * op->kcap,
+                                           fx);
             });
         } else {
             for (int64_t k_lo = 0; k_lo < klocs; k_lo += dz::FOLD_GCAP) {
@@ -2221,7 +2357,7 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                             op->s_max, op->s_sum, op->s_first,
                             (int64_t)op->nslots * 5 * op->kcap, op->d_dbg,
                             op->v_base,
-                            (int64_t)op->nslots * 2 * op->kcap);
+                            (int64_t)op->nslots * 2 * op->kcap, fx);
                     });
                 }
             }
@@ -2251,11 +2387,12 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
  * compute stream, process it before returning (host-batch semantics). */
 static dz_status push_core(dz_window_op* op, int64_t n, const int64_t* d_ts,
                            const int32_t* d_kid, const double* d_vals,
-                           const uint8_t* d_valbm, bool keys_are_dense) {
+                           const uint8_t* d_valbm, bool keys_are_dense,
+                           const dz_window_op::XCols* xc = nullptr) {
     if (process_pending(op) != DZ_OK) return DZ_ERR;
     if (n <= 0) return DZ_OK; /* empty batch: reference emits empty (no-op) */
     if (stage_core(op, n, d_ts, d_kid, d_vals, d_valbm, keys_are_dense,
-                   /*deferred=*/false) != DZ_OK)
+                   /*deferred=*/false, /*borrow=*/false, xc) != DZ_OK)
         return DZ_ERR;
     return process_pending(op);
 }
@@ -2272,11 +2409,66 @@ static dz_status ensure_zero_kid(dz_window_op* op, int64_t n) {
     return DZ_OK;
 }
 
+/* Several value columns: the extras of the NEXT device push. */
+extern "C" dz_status dz_window_op_set_extra_values(
+        dz_window_op* op, int64_t n_rows, const double* const* d_vals,
+        const uint8_t* const* d_validity) {
+    if (!op) return DZ_ERR;
+    if (op->nx == 0) {
+        op->err = "set_extra_values: this operator aggregates one value "
+                  "column (no extra columns declared)";
+        return DZ_ERR;
+    }
+    if (!d_vals) {
+        op->err = "set_extra_values: null column list";
+        return DZ_ERR;
+    }
+    for (int c = 0; c < op->nx; c++)
+        if (!d_vals[c] && n_rows > 0) {
+            op->err = "set_extra_values: extra column " + std::to_string(c + 1) +
+                      " is null";
+            return DZ_ERR;
+        }
+    op->x_att = dz_window_op::XCols();
+    for (int c = 0; c < op->nx; c++) {
+        op->x_att.vals[c] = d_vals[c];
+        op->x_att.valid[c] = d_validity ? d_validity[c] : nullptr;
+    }
+    op->x_att_n = n_rows;
+    op->x_att_on = true;
+    return DZ_OK;
+}
+
+/* A device push's extras: the attachment set_extra_values left, consumed
+ * here. Refuses (op untouched otherwise, handle usable) when a multi-column
+ * op has none or its row count differs; single-column ops take nothing. */
+static dz_status take_extras(dz_window_op* op, int64_t n_rows,
+                             dz_window_op::XCols* xc) {
+    if (op->nx == 0) return DZ_OK;
+    const bool on = op->x_att_on;
+    op->x_att_on = false;
+    if (!on) {
+        op->err = "device push on a multi-column operator needs "
+                  "dz_window_op_set_extra_values first";
+        return DZ_ERR;
+    }
+    if (op->x_att_n != n_rows) {
+        op->err = "extra value columns were set for " +
+                  std::to_string(op->x_att_n) + " rows, the push has " +
+                  std::to_string(n_rows);
+        return DZ_ERR;
+    }
+    *xc = op->x_att;
+    return DZ_OK;
+}
+
 extern "C" dz_status dz_window_op_push_device(dz_window_op* op, int64_t n_rows,
                                               const int64_t* d_ts_ms,
                                               const int32_t* d_key_ids,
                                               const double* d_vals) {
     if (!op) return DZ_ERR;
+    dz_window_op::XCols xc;
+    if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
     if (op->no_group || !d_key_ids) {
         if (ensure_zero_kid(op, n_rows) != DZ_OK) return DZ_ERR;
@@ -2297,7 +2489,8 @@ extern "C" dz_status dz_window_op_push_device(dz_window_op* op, int64_t n_rows,
     dz_window_op::Pend prev = op->pend;
     op->pend.active = false;
     if (stage_core(op, n_rows, d_ts_ms, d_key_ids, d_vals, nullptr,
-                   /*keys_are_dense=*/true, /*deferred=*/true) != DZ_OK)
+                   /*keys_are_dense=*/true, /*deferred=*/true,
+                   /*borrow=*/false, &xc) != DZ_OK)
         return DZ_ERR;
     if (prev.active) return process_batch(op, prev);
     return DZ_OK;
@@ -2313,6 +2506,8 @@ extern "C" dz_status dz_window_op_push_device_borrowed(
         dz_window_op* op, int64_t n_rows, const int64_t* d_ts_ms,
         const int32_t* d_key_ids, const double* d_vals) {
     if (!op) return DZ_ERR;
+    dz_window_op::XCols xc;
+    if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
     if (op->no_group || !d_key_ids) {
         if (ensure_zero_kid(op, n_rows) != DZ_OK) return DZ_ERR;
@@ -2330,7 +2525,7 @@ extern "C" dz_status dz_window_op_push_device_borrowed(
     op->pend.active = false;
     if (stage_core(op, n_rows, d_ts_ms, d_key_ids, d_vals, nullptr,
                    /*keys_are_dense=*/true, /*deferred=*/true,
-                   /*borrow=*/true) != DZ_OK)
+                   /*borrow=*/true, &xc) != DZ_OK)
         return DZ_ERR;
     if (prev.active) return process_batch(op, prev);
     return DZ_OK;
@@ -2479,6 +2674,8 @@ extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
                   "operator (two dictionaries would assign conflicting ids)";
         return DZ_ERR;
     }
+    dz_window_op::XCols xc;
+    if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
     if (n_rows <= 0) return process_pending(op);
     int C = (int)std::min<int64_t>(512,
@@ -2506,7 +2703,7 @@ extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
     });
     if (stage_core(op, n_rows, d_ts_ms, op->d_ikid[b], d_vals, nullptr,
                    /*keys_are_dense=*/true, /*deferred=*/true,
-                   /*borrow=*/true) != DZ_OK)
+                   /*borrow=*/true, &xc) != DZ_OK)
         return DZ_ERR;
     if (prev.active) return process_batch(op, prev);
     return DZ_OK;
@@ -2531,6 +2728,8 @@ extern "C" dz_status dz_window_op_push_device_i64(dz_window_op* op,
         op->err = "push_device_i64: d_keys must be 8-byte aligned";
         return DZ_ERR;
     }
+    dz_window_op::XCols xc;
+    if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
     if (n_rows <= 0) return process_pending(op);
     int C = (int)std::min<int64_t>(512,
@@ -2555,7 +2754,7 @@ extern "C" dz_status dz_window_op_push_device_i64(dz_window_op* op,
     });
     if (stage_core(op, n_rows, d_ts_ms, op->d_ikid[b], d_vals, nullptr,
                    /*keys_are_dense=*/true, /*deferred=*/true,
-                   /*borrow=*/true) != DZ_OK)
+                   /*borrow=*/true, &xc) != DZ_OK)
         return DZ_ERR;
     if (prev.active) return process_batch(op, prev);
     return DZ_OK;
@@ -2594,17 +2793,21 @@ extern "C" dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch) 
     const dz_column& tsc = batch->cols[op->ts_col];
     static const dz_column k_none = {0, nullptr, nullptr, nullptr};
     const dz_column& kc = op->no_group ? k_none : batch->cols[op->group_col];
-    const dz_column& vc = batch->cols[op->aggs[0].input_col];
-    for (auto& a : op->aggs)
-        if (a.input_col != op->aggs[0].input_col) {
-            op->err = "all aggregates must share one input column (hot-path shape)";
+    const dz_column& vc = batch->cols[op->dcols[0]];
+    for (int c = 0; c <= op->nx; c++)
+        if (op->dcols[c] < 0 || !batch->cols[op->dcols[c]].data) {
+            op->err = "value column " + std::to_string(op->dcols[c]) +
+                      " has no data";
             return DZ_ERR;
         }
 
     CHK(op, hipSetDevice(op->device));
     /* staging buffers */
     size_t bm_bytes = (size_t)((n + 7) / 8);
-    size_t stage = (size_t)n * (8 + 4 + 8) + bm_bytes + 64;
+    /* the extras stage behind the primary: values, then 8-aligned bitmaps */
+    const size_t bm_pad = (bm_bytes + 7) & ~(size_t)7;
+    size_t stage = (size_t)n * (8 + 4 + 8) + bm_pad + 64 +
+                   (size_t)op->nx * ((size_t)n * 8 + bm_pad);
     if (stage > op->h_stage_cap) {
         if (op->h_stage) hipHostFree(op->h_stage);
         CHK(op, hipHostMalloc((void**)&op->h_stage, stage));
@@ -2616,6 +2819,11 @@ extern "C" dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch) 
         CHK(op, hipMalloc(&op->d_kid, (size_t)n * 4));
         CHK(op, hipMalloc(&op->d_vals, (size_t)n * 8));
         CHK(op, hipMalloc(&op->d_valbm, bm_bytes ? bm_bytes : 1));
+        for (int c = 0; c < op->nx; c++) {
+            hipFree(op->d_xvals[c]); hipFree(op->d_xbm[c]);
+            CHK(op, hipMalloc(&op->d_xvals[c], (size_t)n * 8));
+            CHK(op, hipMalloc(&op->d_xbm[c], bm_bytes ? bm_bytes : 1));
+        }
         op->in_cap = n;
     }
     int64_t* h_ts = (int64_t*)op->h_stage;
@@ -2692,10 +2900,29 @@ extern "C" dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch) 
     CHK(op, hipMemcpyAsync(op->d_vals, h_vals, (size_t)n * 8, hipMemcpyHostToDevice, op->stream));
     if (have_bm)
         CHK(op, hipMemcpyAsync(op->d_valbm, h_bm, bm_bytes, hipMemcpyHostToDevice, op->stream));
+    dz_window_op::XCols xc;
+    {
+        char* h_x = (char*)h_bm + bm_pad;
+        for (int c = 0; c < op->nx; c++) {
+            const dz_column& xcol = batch->cols[op->dcols[c + 1]];
+            memcpy(h_x, xcol.data, (size_t)n * 8);
+            CHK(op, hipMemcpyAsync(op->d_xvals[c], h_x, (size_t)n * 8,
+                                   hipMemcpyHostToDevice, op->stream));
+            h_x += (size_t)n * 8;
+            xc.vals[c] = op->d_xvals[c];
+            if (xcol.validity) {
+                memcpy(h_x, xcol.validity, bm_bytes);
+                CHK(op, hipMemcpyAsync(op->d_xbm[c], h_x, bm_bytes,
+                                       hipMemcpyHostToDevice, op->stream));
+                xc.valid[c] = op->d_xbm[c];
+            }
+            h_x += bm_pad;
+        }
+    }
 
     return push_core(op, n, op->d_ts, op->d_kid, op->d_vals,
                      have_bm ? op->d_valbm : nullptr,
-                     op->key_kind == DZ_KEY_DENSE_INT64);
+                     op->key_kind == DZ_KEY_DENSE_INT64, &xc);
 }
 
 /* ------------------------------------------------------------------ */
@@ -2803,11 +3030,12 @@ extern "C" dz_status dz_window_op_poll(dz_window_op* op, const dz_out_batch** ou
     }
     ob.view.agg_cols = ob.agg_ptrs.data();
     ob.view.agg_valid_cols = nullptr;
-    if (op->has_var) {
+    if (op->has_var || op->nx > 0) {
         ob.valid_ptrs.clear();
         for (size_t a = 0; a < op->aggs.size(); a++)
             ob.valid_ptrs.push_back(
-                is_var_op(op->aggs[a].op) && a < ob.agg_valid_a.size()
+                (is_var_op(op->aggs[a].op) || op->agg_col[a] > 0) &&
+                        a < ob.agg_valid_a.size()
                     ? ob.agg_valid_a[a].data() : nullptr);
         ob.view.agg_valid_cols = ob.valid_ptrs.data();
     }

@@ -27,6 +27,15 @@ def merge_global_partials(per_rank_batches):
                     f"merge_global_partials cannot merge {bad}: combining "
                     "Welford (count, mean, m2) partials needs a different "
                     "formula than count/min/max/sum and is not supported")
+            # an aggregate on an extra value column reports its own mask as
+            # "<name>_valid": such batches carry several columns' partials
+            extra = sorted(k for k in b if k.endswith("_valid")
+                           and k[:-len("_valid")] not in _VAR_NAMES)
+            if extra:
+                raise ValueError(
+                    f"merge_global_partials cannot merge batches of a "
+                    f"multi-column op ({extra}): it combines one value "
+                    "column's count/min/max/sum partials only")
     acc = {}  # (wstart, wend) -> [count, min, max, sum, any_valid]
     order = []
     for batches in per_rank_batches:

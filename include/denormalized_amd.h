@@ -71,8 +71,21 @@ typedef struct dz_agg_desc {
  * (mode, group-by, aggregate exprs, window type) —
  * crates/core/src/planner/streaming_window.rs:133-165 and
  * StreamingWindowExec::new (physical_plan/continuous/streaming_window.rs:201+).
- * This build supports the hot path's shape: one group column, aggregates over
- * one f64 value column, mode Single (grouped). */
+ * This build supports the hot path's shape: one group column, mode Single
+ * (grouped), aggregates over up to DZ_MAX_VALUE_COLS distinct f64 value
+ * columns (the reference aggregates several columns in one window:
+ * examples/examples/kafka_rideshare.rs:73-75).
+ *
+ * Several value columns. The distinct input_col values are numbered in order
+ * of first appearance in aggs: column 0 (aggs[0].input_col) is the primary,
+ * columns 1..X the extras. Every column has its own validity bitmap, so
+ * count(c) and the NULL-ness of min/max/sum/avg(c) are per column; a group
+ * exists as soon as it has a row, whatever is NULL in it. Each column's
+ * accumulators see that column's valid rows in row order (bit-exact f64 sum).
+ * dz_window_op_create returns NULL for more than DZ_MAX_VALUE_COLS distinct
+ * columns, and for a variance-family aggregate together with more than one
+ * distinct column: the variance family stays single-column in this version. */
+#define DZ_MAX_VALUE_COLS 4
 typedef struct dz_window_desc {
     dz_window_type window_type;
     int64_t length_ms;
@@ -134,7 +147,11 @@ typedef struct dz_out_batch {
      * a; a NULL entry means that aggregate follows agg_valid. The variance
      * family has its own NULL rule (var_samp of a one-row group is NULL
      * while its min is valid), so its entries are non-NULL. The pointer
-     * itself may be NULL for ops that declare no variance aggregate. */
+     * itself may be NULL for ops that declare no variance aggregate.
+     * Multi-column ops: agg_valid is the PRIMARY column's mask; every
+     * aggregate on an extra column has a non-NULL entry here (1 while that
+     * column has a valid row in the group; all 1 for count, which is never
+     * NULL), entries of primary-column aggregates stay NULL. */
     const uint8_t* const* agg_valid_cols;
 } dz_out_batch;
 
@@ -154,8 +171,25 @@ dz_window_op* dz_window_op_create(const dz_window_desc* desc);
 /* One input batch == one poll of the input stream
  * (poll_next_inner: grouped_window_agg_stream.rs:326-420): computes the batch
  * watermark, ensures window frames, routes + aggregates rows, advances the
- * shared watermark, triggers closed windows. */
+ * shared watermark, triggers closed windows. Each aggregate reads its values
+ * and its validity bitmap from batch->cols[input_col]. */
 dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch);
+
+/* Extra value columns (distinct input columns 1..X, in order of first
+ * appearance in aggs) for the NEXT device push of any kind. d_validity may be
+ * NULL, and any entry may be NULL (all valid); bitmaps are Arrow LSB-first.
+ * Borrowed: columns and bitmaps stay valid and unmodified until the call
+ * AFTER that push, also when the push itself is the staging variant.
+ * The attachment is consumed by one push (a refused one included). DZ_ERR
+ * with a message, the op left usable, when this is called on a single-column
+ * op, when a device push on a multi-column op was not preceded by it, and
+ * when its n_rows differs from the push's n_rows (the last two are reported
+ * by the push). The primary column of a device push has no validity bitmap.
+ * Multi-column ops build every emitted batch on the host (as the variance
+ * family does), at every key count. */
+dz_status dz_window_op_set_extra_values(dz_window_op* op, int64_t n_rows,
+                                        const double* const* d_vals,
+                                        const uint8_t* const* d_validity);
 
 /* Device-resident push: same results as dz_window_op_push but the three
  * buffers already live in the op's device HBM (keys as dense int32 ids).
@@ -250,7 +284,8 @@ int64_t dz_window_op_open_windows(dz_window_op* op);
  * into the operator's emission keeps the boundary drop-in (output batches
  * are already filtered). cmp: 0 '<', 1 '<=', 2 '>', 3 '>=', 4 '==', 5 '!='.
  * agg_idx indexes dz_window_desc.aggs. NULL aggregate values never pass
- * (for the variance family: the finalised value, under its own NULL rule). */
+ * (for the variance family: the finalised value, under its own NULL rule;
+ * for an aggregate on an extra value column: that column's own NULL-ness). */
 dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
                                   int32_t cmp, double literal);
 
