@@ -12,7 +12,9 @@
  *   k_scan_*   bucket bases + per-chunk stable offsets
  *   k_scatter  stable partition: records (meta,rowidx,value) land in bucket
  *              regions IN GLOBAL ROW ORDER (weighted intra-wave ranks via
- *              wave-64 shuffles + wave-serialized LDS cursors)
+ *              wave-64 shuffles + wave-serialized LDS cursors);
+ *              k_scatter_tumbling is the same partition for plain tumbling
+ *              batches, each row read once and held in registers
  *   k_regroup_t<RG_*_FOLD>  one block per bucket (or (bucket,bin1) segment):
  *              stable per-supertile split of the bucket's records into
  *              per-(window,key) bins IN LDS, then each bin's staged segment
@@ -827,7 +829,10 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(const int32_t* kid,
         uint32_t* dbg) {
     /* LDS-staged stable partition. Each wave owns a CONTIGUOUS QUARTER of the
      * supertile (wave order == row order), so staging cursors are per-wave
-     * private: no cross-wave serialization, ~4 block barriers per supertile.
+     * private: no cross-wave serialization. A supertile costs 23 block
+     * barriers here, 17 of them in the Hillis-Steele prefix; this kernel now
+     * serves only the sliding and subrange-split launches (the plain
+     * tumbling batch runs k_scatter_tumbling below: 4 barriers, one read).
      * Records are placed bucket-major in LDS and flushed so adjacent lanes
      * write adjacent global addresses (the direct form measured 6x write
      * amplification — profiles/hbm_traffic.json). A sector-aligned carrying
@@ -1000,14 +1005,226 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(const int32_t* kid,
     }
 }
 
+/* inclusive scan of one value per lane over the wave, in registers */
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+/* exclusive prefix of one partial per thread over the block, and the block
+ * total: a wave scan plus the four wave totals through wtot[] — ONE block
+ * barrier (the Hillis-Steele form through LDS took 17). wtot[] must not be
+ * written again before another barrier has passed. */
+__device__ __forceinline__ uint32_t block_scan_excl(uint32_t s, uint32_t* wtot,
+                                                    uint32_t* total) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_scan_incl(s, lane);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
+        const uint32_t t = wtot[w];
+        if (w < wave) pre += t;
+        tot += t;
+    }
+    *total = tot;
+    return pre + incl - s;
+}
+
+/* rows (scatter) or records (regroup) one lane holds per supertile: a wave's
+ * quarter is at most ST_RECORDS / 4 = 512 = 8 lane-strided iterations */
+constexpr int ST_SLOTS = ST_RECORDS / BLOCK;
+
+/* wave-quarter bounds of the supertile [st0, st1) (contiguous: wave order ==
+ * row order) */
+template <typename T>
+__device__ __forceinline__ void wave_quarter(T st0, T st1, int wave, T* w0,
+                                             T* w1) {
+    const T q = ((st1 - st0) + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    *w0 = st0 + wave * q < st1 ? st0 + wave * q : st1;
+    *w1 = *w0 + q < st1 ? *w0 + q : st1;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
+        const int64_t* ts, const double* vals, const uint8_t* validity,
+        int64_t n, int64_t chunk, WinParams wp, const uint32_t* gofs,
+        uint4* grec, uint32_t rec_limit, uint32_t* dbg) {
+    /* k_scatter for the plain tumbling batch (every row lands in exactly one
+     * window, supertiles of ST_RECORDS rows): the same wave-quarter counts,
+     * bin prefix, ballot-ranked placement and bucket-major flush, so every
+     * record lands where k_scatter puts it — but each row's kid, ts, value
+     * and validity bit are read ONCE, into ST_SLOTS register slots per lane,
+     * counted and placed from there; the loads of supertile s+1 are issued
+     * before supertile s is counted, so their latency runs under its whole
+     * chain; and the chain is 4 block barriers (count | wave totals |
+     * cursors | placement) instead of 23: the chunk's global cursors live in
+     * their owner thread's registers, and each wave re-zeroes its own count
+     * row, which nobody else reads until the next prefix. */
+    __shared__ uint32_t cnt4[WAVES_PER_BLOCK][NB]; /* per-wave-quarter counts,
+                                     * converted IN PLACE to per-wave staging
+                                     * cursors by the prefix */
+    __shared__ uint32_t offs[NB];   /* per-supertile exclusive bin prefix     */
+    __shared__ uint32_t dbase[NB];  /* global cursor - offs: dest = dbase + p */
+    __shared__ uint4 s_rec[ST_RECORDS];
+    __shared__ uint32_t s_wtot[WAVES_PER_BLOCK];
+    auto wofs = cnt4;
+    constexpr int PER = NB / BLOCK;
+    constexpr uint32_t SENT = 0xFFFFFFFFu;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t lo = blockIdx.x * chunk;
+    const int64_t hi = i64min(n, lo + chunk);
+    if (lo >= hi) return;
+    uint32_t cur[PER]; /* global cursors of this thread's PER bins */
+#pragma unroll
+    for (int j = 0; j < PER; j++)
+        cur[j] = gofs[(int64_t)blockIdx.x * NB + threadIdx.x * PER + j];
+    for (int t = lane; t < NB; t += 64) cnt4[wave][t] = 0;
+
+    /* the supertile's rows as loaded; rows past the quarter's end re-read the
+     * chunk's last row (always in bounds) and are masked out below */
+    int32_t n_kid[ST_SLOTS];
+    int64_t n_ts[ST_SLOTS];
+    double n_val[ST_SLOTS];
+    uint32_t n_vb[ST_SLOTS];
+    auto load_rows = [&](int64_t st0) {
+        int64_t w0, w1;
+        wave_quarter(st0, i64min(hi, st0 + ST_RECORDS), wave, &w0, &w1);
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++) {
+            const int64_t i = i64min(w0 + k * 64 + lane, hi - 1);
+            n_kid[k] = kid[i];
+            n_ts[k] = ts[i];
+            n_val[k] = vals[i];
+            n_vb[k] = validity ? (uint32_t)validity[i >> 3] : 0xFFu;
+        }
+    };
+    load_rows(lo);
+
+    for (int64_t st0 = lo; st0 < hi; st0 += ST_RECORDS) {
+        int64_t w0, w1;
+        wave_quarter(st0, i64min(hi, st0 + ST_RECORDS), wave, &w0, &w1);
+        /* this supertile's rows: bucket (SENT = no row), meta word, value */
+        uint32_t bk[ST_SLOTS], meta[ST_SLOTS];
+        uint64_t vb[ST_SLOTS];
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++) {
+            const int64_t i = w0 + k * 64 + lane;
+            const uint32_t kv = (uint32_t)n_kid[k];
+            const uint32_t valid = (n_vb[k] >> (i & 7)) & 1u;
+            int32_t jmin, m;
+            row_windows(n_ts[k], wp, &jmin, &m);
+            bk[k] = i < w1 ? (kv & (NB - 1)) : SENT;
+            meta[k] = (kv >> LOG_NB) | ((uint32_t)jmin << META_WIDX_SHIFT)
+                    | (valid << META_VALID_SHIFT);
+            vb[k] = (uint64_t)__double_as_longlong(n_val[k]);
+        }
+        if (st0 + ST_RECORDS < hi) load_rows(st0 + ST_RECORDS);
+        /* counts per (wave, bucket), from registers */
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++)
+            if (bk[k] != SENT) atomicAdd(&cnt4[wave][bk[k]], 1u);
+        __syncthreads();
+        /* per-supertile prefix: offs (bin-major) + per-wave staging bases */
+        uint32_t tot;
+        {
+            uint32_t excl[PER];
+            uint32_t s = 0;
+#pragma unroll
+            for (int j = 0; j < PER; j++) {
+                const int b = threadIdx.x * PER + j;
+                uint32_t t = 0;
+                for (int w = 0; w < WAVES_PER_BLOCK; w++) t += cnt4[w][b];
+                excl[j] = s;
+                s += t;
+            }
+            const uint32_t pre = block_scan_excl(s, s_wtot, &tot);
+#pragma unroll
+            for (int j = 0; j < PER; j++) {
+                const int b = threadIdx.x * PER + j;
+                uint32_t run = pre + excl[j];
+                offs[b] = run;
+                dbase[b] = cur[j] - run;
+                for (int w = 0; w < WAVES_PER_BLOCK; w++) {
+                    const uint32_t c = cnt4[w][b];
+                    wofs[w][b] = run; /* overlays cnt4 */
+                    run += c;
+                }
+                cur[j] += run - (pre + excl[j]); /* the bin's total */
+            }
+        }
+        __syncthreads();
+        /* ranked placement from registers, PER-WAVE private cursors, in the
+         * row order the counts were taken in */
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++) {
+            if (w0 + k * 64 >= w1) break; /* wave-uniform */
+            const uint32_t bkt = bk[k];
+            /* bit-ballot same-bucket mask (9+1 bits incl SENT) */
+            uint64_t same = ~0ULL;
+            for (int b = 0; b < 9; b++) {
+                uint64_t bb = __ballot((bkt >> b) & 1);
+                same &= ((bkt >> b) & 1) ? bb : ~bb;
+            }
+            {
+                uint64_t bb = __ballot(bkt == SENT);
+                same &= (bkt == SENT) ? bb : ~bb;
+            }
+            const uint64_t below =
+                (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
+            const uint32_t r = (uint32_t)__popcll(same & below) - 1;
+            const uint32_t wtot = (uint32_t)__popcll(same);
+            const int fl = __ffsll((unsigned long long)same) - 1;
+            uint32_t pre = 0;
+            if (lane == fl && bkt != SENT) {
+                pre = wofs[wave][bkt];
+                wofs[wave][bkt] = pre + wtot;
+            }
+            pre = (uint32_t)__shfl((int)pre, fl);
+            if (bkt != SENT)
+                s_rec[pre + r] = make_uint4(
+                    (uint32_t)vb[k], (uint32_t)(vb[k] >> 32),
+                    (uint32_t)(w0 + k * 64 + lane), meta[k]);
+        }
+        /* own count row back to zero for the next supertile (only this wave
+         * touches it until the next prefix, two barriers on) */
+        for (int t = lane; t < NB; t += 64) cnt4[wave][t] = 0;
+        __syncthreads();
+        /* flush: bucket-major staging => coalesced run writes; the record's
+         * bin (and so its destination) falls out of a binary search over
+         * the bin prefix. No barrier after it: nothing it reads is written
+         * again before the next supertile's first barrier. */
+        for (uint32_t p = threadIdx.x; p < tot; p += BLOCK) {
+            uint32_t b = 0;
+            for (int stp = NB >> 1; stp; stp >>= 1)
+                if (b + stp < NB && offs[b + stp] <= p) b += stp;
+            const uint32_t d = dbase[b] + p;
+            if (d < rec_limit) grec[d] = s_rec[p];
+            else dbg[0] = 1; /* bounds guard: flag, never corrupt */
+        }
+    }
+}
+
 void launch_scatter(hipStream_t s, const int32_t* d_kid, const int64_t* d_ts,
                     const double* d_vals, const uint8_t* d_validity, int64_t n,
                     int64_t chunk, int C, int32_t st_rows, const WinParams& wp,
                     const uint32_t* d_gofs, uint4* d_grec, uint32_t rec_limit,
                     uint32_t* d_dbg) {
-    hipLaunchKernelGGL(k_scatter, dim3(C), dim3(BLOCK), 0, s, d_kid, d_ts, d_vals,
-                       d_validity, n, chunk, st_rows, wp, d_gofs, d_grec,
-                       rec_limit, d_dbg);
+    if (!wp.is_sliding && st_rows == ST_RECORDS)
+        hipLaunchKernelGGL(k_scatter_tumbling, dim3(C), dim3(BLOCK), 0, s,
+                           d_kid, d_ts, d_vals, d_validity, n, chunk, wp,
+                           d_gofs, d_grec, rec_limit, d_dbg);
+    else
+        hipLaunchKernelGGL(k_scatter, dim3(C), dim3(BLOCK), 0, s, d_kid, d_ts,
+                           d_vals, d_validity, n, chunk, st_rows, wp, d_gofs,
+                           d_grec, rec_limit, d_dbg);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1103,8 +1320,7 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     __shared__ uint32_t wcur[WAVES_PER_BLOCK][GCAP];   /* per-wave cursors */
     __shared__ uint32_t s_dest[ST_RECORDS]; /* RG_L1 only */
     __shared__ uint4 s_rec[ST_RECORDS];     /* meta travels in .w */
-    __shared__ uint32_t scanbuf[BLOCK];
-    __shared__ uint32_t s_total;
+    __shared__ uint32_t s_wtot[WAVES_PER_BLOCK];
     static_assert(GCAP == BLOCK, "parallel bin prefix maps one thread per bin");
 
     const int bkt = blockIdx.x;
@@ -1236,37 +1452,66 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
             binlens[obase + g] = cnt[g];
         }
     }
+    /* Per supertile each record is read ONCE, into ST_SLOTS register slots
+     * per lane; bins are counted and records placed from those registers.
+     * The next supertile's records are loaded (into nxt) before this one is
+     * counted, so their latency runs under its whole chain. 4 block barriers
+     * per supertile: count | wave totals | cursors | placement. Each wave
+     * re-zeroes its own count row after placing (nobody else reads it until
+     * the next prefix), and nothing read after the last barrier is written
+     * again before the next supertile's first, so the fold walk (or the L1
+     * flush) needs none behind it. */
+    /* two or three extra columns' accumulators leave no room for the second
+     * register set (179 and 195 VGPRs: past the 168 that 3 waves/SIMD
+     * allow): those instantiations load each supertile where it is taken
+     * over */
+    constexpr bool PREFETCH = NX < 2;
+    for (int g = lane; g < GCAP; g += 64) stcnt4[wave][g] = 0;
+    uint4 nxt[ST_SLOTS];
+    /* slots past the quarter's end re-read the segment's last record (always
+     * in bounds) and are masked out when the set is taken over */
+    auto load_recs = [&](uint32_t st0) {
+        uint32_t w0, w1;
+        wave_quarter<uint32_t>(st0, min(hi, st0 + (uint32_t)ST_RECORDS), wave,
+                               &w0, &w1);
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++)
+            nxt[k] = rrec[min(w0 + (uint32_t)(k * 64 + lane), hi - 1)];
+    };
+    if (PREFETCH && lo < hi) load_recs(lo);
     for (uint32_t st0 = lo; st0 < hi; st0 += ST_RECORDS) {
-        const uint32_t st1 = min(hi, st0 + (uint32_t)ST_RECORDS);
-        /* wave-quarter bounds (contiguous: wave order == row order) */
-        const uint32_t q = ((st1 - st0) + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const uint32_t w0 = min(st1, st0 + (uint32_t)wave * q);
-        const uint32_t w1 = min(st1, w0 + q);
-        for (int g = threadIdx.x; g < GCAP; g += BLOCK)
-            for (int w = 0; w < WAVES_PER_BLOCK; w++) stcnt4[w][g] = 0;
-        __syncthreads();
-        for (uint32_t i = w0 + lane; i < w1; i += 64) {
-            const uint32_t g = bin_of(rrec[i].w);
-            if (g != 0x1FFu) atomicAdd(&stcnt4[wave][g], 1u);
+        uint32_t w0, w1;
+        wave_quarter<uint32_t>(st0, min(hi, st0 + (uint32_t)ST_RECORDS), wave,
+                               &w0, &w1);
+        uint4 recs[ST_SLOTS];
+        uint32_t bins[ST_SLOTS];
+        if (!PREFETCH) load_recs(st0);
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++) {
+            recs[k] = nxt[k];
+            uint32_t g = 0x1FFu; /* sentinel above GCAP-1 */
+            if (w0 + (uint32_t)(k * 64 + lane) < w1) g = bin_of(recs[k].w);
+            /* fold records carry validity in bit 31; L1 passes the
+             * raw rowidx through (meta stays in .w) */
+            if (MODE != RG_L1 && g != 0x1FFu)
+                recs[k].z |= (recs[k].w >> META_VALID_SHIFT) << 31;
+            bins[k] = g;
         }
+        if (PREFETCH && st0 + (uint32_t)ST_RECORDS < hi &&
+            st0 + (uint32_t)ST_RECORDS > st0)
+            load_recs(st0 + ST_RECORDS);
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++)
+            if (bins[k] != 0x1FFu) atomicAdd(&stcnt4[wave][bins[k]], 1u);
         __syncthreads();
-        {   /* parallel bin prefix (GCAP == BLOCK: one thread per bin) — the
-             * serial thread-0 form cost ~1k lone LDS reads per supertile */
-            uint32_t tg = 0;
-            for (int w = 0; w < WAVES_PER_BLOCK; w++)
-                tg += stcnt4[w][threadIdx.x];
-            scanbuf[threadIdx.x] = tg;
-            __syncthreads();
-            for (int o = 1; o < BLOCK; o <<= 1) {
-                uint32_t v =
-                    (threadIdx.x >= (unsigned)o) ? scanbuf[threadIdx.x - o] : 0;
-                __syncthreads();
-                scanbuf[threadIdx.x] += v;
-                __syncthreads();
-            }
-            uint32_t run = threadIdx.x ? scanbuf[threadIdx.x - 1] : 0;
+        /* parallel bin prefix (GCAP == BLOCK: one thread per bin) */
+        uint32_t tg = 0, s_total;
+        for (int w = 0; w < WAVES_PER_BLOCK; w++)
+            tg += stcnt4[w][threadIdx.x];
+        const uint32_t seg0 = block_scan_excl(tg, s_wtot, &s_total);
+        {
+            uint32_t run = seg0;
             stoffs[threadIdx.x] = run;
-            if (threadIdx.x == BLOCK - 1) s_total = scanbuf[threadIdx.x];
             for (int w = 0; w < WAVES_PER_BLOCK; w++) { /* per-wave bases */
                 wcur[w][threadIdx.x] = run;
                 run += stcnt4[w][threadIdx.x];
@@ -1274,18 +1519,11 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
         }
         __syncthreads();
         /* ranked placement into staging, per-wave private cursors */
-        for (uint32_t t0 = w0; t0 < w1; t0 += 64) {
-            const uint32_t i = t0 + lane;
-            uint32_t g = 0x1FFu; /* sentinel above GCAP-1 */
-            uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-            if (i < w1) {
-                rec = rrec[i];
-                g = bin_of(rec.w);
-                /* fold records carry validity in bit 31; L1 passes the
-                 * raw rowidx through (meta stays in .w) */
-                if (MODE != RG_L1 && g != 0x1FFu)
-                    rec.z |= (rec.w >> META_VALID_SHIFT) << 31;
-            }
+#pragma unroll
+        for (int k = 0; k < ST_SLOTS; k++) {
+            if (w0 + (uint32_t)(k * 64) >= w1) break; /* wave-uniform */
+            const uint32_t g = bins[k];
+            const uint4 rec = recs[k];
             /* same-bin mask via bit-ballots over the 9 bin-id bits */
             uint64_t same = ~0ULL;
             for (int b = 0; b < 9; b++) {
@@ -1312,14 +1550,13 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                     s_dest[pos] = lo + gcur[g] + (pos - stoffs[g]);
             }
         }
+        for (int g = lane; g < GCAP; g += 64) stcnt4[wave][g] = 0;
         __syncthreads();
         if (FOLD) {
             /* consume the staging in place: thread t folds bin t's staged
              * segment (row-ordered) into its register accumulator — the
              * reference's sequential update_batch order, no HBM round-trip */
-            const int g = threadIdx.x;
-            const uint32_t seg0 = stoffs[g];
-            const uint32_t seg1 = (g + 1 < GCAP) ? stoffs[g + 1] : s_total;
+            const uint32_t seg1 = seg0 + tg;
             if (f_own && seg1 > seg0) {
                 if (!f_loaded) { /* lazy seed at the bin's first record */
                     f_loaded = true;
@@ -1391,19 +1628,13 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                     }
                 }
             }
-            __syncthreads();
         } else {
-            /* L1 flush (bin-major staging => coalesced runs) */
-            const uint32_t tot = s_total;
-            for (uint32_t p = threadIdx.x; p < tot; p += BLOCK)
+            /* L1 flush (bin-major staging => coalesced runs); the bin's
+             * owner advances its segment cursor, which only the placement
+             * phase reads */
+            gcur[threadIdx.x] += tg;
+            for (uint32_t p = threadIdx.x; p < s_total; p += BLOCK)
                 orec[s_dest[p]] = s_rec[p];
-            __syncthreads();
-            for (int g = threadIdx.x; g < GCAP; g += BLOCK) {
-                uint32_t s = 0;
-                for (int w = 0; w < WAVES_PER_BLOCK; w++) s += stcnt4[w][g];
-                gcur[g] += s;
-            }
-            __syncthreads();
         }
     }
     if (FOLD && f_own && f_loaded) { /* untouched bins write nothing */
