@@ -1466,6 +1466,10 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
      * allow): those instantiations load each supertile where it is taken
      * over */
     constexpr bool PREFETCH = NX < 2;
+    /* staged records the fold walk reads ahead of their updates; the group
+     * lives in the registers recs[]/bins[] vacate after placement, and the
+     * gathered extras of NX >= 2 leave room for half a group */
+    constexpr int WALK_G = NX < 2 ? 8 : 4;
     for (int g = lane; g < GCAP; g += 64) stcnt4[wave][g] = 0;
     uint4 nxt[ST_SLOTS];
     /* slots past the quarter's end re-read the segment's last record (always
@@ -1596,37 +1600,86 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                 }
                 if (f_fst == ~0ULL)
                     f_fst = fc.row_base + (s_rec[seg0].z & 0x7FFFFFFFu);
-                for (uint32_t r = seg0; r < seg1; r++) {
-                    const uint4 rec = s_rec[r];
-                    const double v = __longlong_as_double(
-                        (long long)(((uint64_t)rec.y << 32) | rec.x));
-                    if (rec.z >> 31) {
-                        const bool fresh = f_cnt == 0;
-                        f_mn = (fresh || v < f_mn) ? v : f_mn;
-                        f_mx = (fresh || v > f_mx) ? v : f_mx;
-                        f_sm += v;
-                        f_cnt++;
-                        if (VAR) welford_step(v, f_cnt, f_mean, f_m2);
+                /* The walk, WALK_G records at a time. The lanes of a wave
+                 * walk in lock step and a supertile's records sit in a few
+                 * long segments, so a loop that reads one record, waits and
+                 * updates pays the LDS round trip once per record of the
+                 * longest segment. Here every read of the group (and every
+                 * gather of an extra column) is issued before the first
+                 * update; the updates then run strictly in record order.
+                 * Only the 12 bytes the fold uses are read. The last group
+                 * is the same code with its slots past seg1 clamped to the
+                 * segment's last record and masked out: a scalar tail would
+                 * cost the wave up to WALK_G - 1 round trips again. Null and
+                 * masked records go through selects, so the body has no
+                 * branch; the valid count runs in 32 bits (a supertile holds
+                 * 2,048 records) and joins f_cnt behind the loop. */
+                bool fresh = f_cnt == 0;
+                uint32_t nv = 0;
+                for (uint32_t r = seg0; r < seg1; r += WALK_G) {
+                    uint2 gv[WALK_G];
+                    uint32_t gz[WALK_G];
+                    [[maybe_unused]] double gxv[WALK_G][NX > 0 ? NX : 1];
+                    [[maybe_unused]] uint32_t gxb[WALK_G][NX > 0 ? NX : 1];
+#pragma unroll
+                    for (int i = 0; i < WALK_G; i++) {
+                        const uint32_t q = min(r + (uint32_t)i, seg1 - 1);
+                        gv[i] = *reinterpret_cast<const uint2*>(&s_rec[q]);
+                        gz[i] = s_rec[q].z;
                     }
                     if constexpr (NX > 0) {
                         const FoldExtras& fx = pick_fx(xa...);
-                        /* extras: gathered by batch row index, each under
-                         * its own validity bit, whatever the primary's is */
-                        const uint32_t row = rec.z & 0x7FFFFFFFu;
+                        /* extras: gathered by batch row index (a masked
+                         * slot re-reads the last record's row: in bounds) */
 #pragma unroll
-                        for (int c = 0; c < NX; c++) {
-                            const uint8_t* bm = fx.valid[c];
-                            if (!bm || ((bm[row >> 3] >> (row & 7)) & 1)) {
-                                const double xv = fx.vals[c][row];
+                        for (int i = 0; i < WALK_G; i++) {
+                            const uint32_t row = gz[i] & 0x7FFFFFFFu;
+#pragma unroll
+                            for (int c = 0; c < NX; c++) {
+                                const uint8_t* bm = fx.valid[c];
+                                gxb[i][c] = bm ? (uint32_t)bm[row >> 3] : 0xFFu;
+                                gxv[i][c] = fx.vals[c][row];
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < WALK_G; i++) {
+                        const bool in = r + (uint32_t)i < seg1;
+                        const double v = __longlong_as_double(
+                            (long long)(((uint64_t)gv[i].y << 32) | gv[i].x));
+                        const bool ok = in && (gz[i] >> 31);
+                        f_mn = (ok && (fresh || v < f_mn)) ? v : f_mn;
+                        f_mx = (ok && (fresh || v > f_mx)) ? v : f_mx;
+                        f_sm = ok ? f_sm + v : f_sm;
+                        nv += ok ? 1u : 0u;
+                        fresh = fresh && !ok;
+                        if (VAR) {
+                            double mean = f_mean, m2 = f_m2;
+                            welford_step(v, f_cnt + nv, mean, m2);
+                            f_mean = ok ? mean : f_mean;
+                            f_m2 = ok ? m2 : f_m2;
+                        }
+                        if constexpr (NX > 0) {
+                            /* each extra under its own validity bit,
+                             * whatever the primary's is */
+                            const uint32_t row = gz[i] & 0x7FFFFFFFu;
+#pragma unroll
+                            for (int c = 0; c < NX; c++) {
+                                const bool xok =
+                                    in && ((gxb[i][c] >> (row & 7)) & 1u);
+                                const double xv = gxv[i][c];
                                 const bool xfresh = x.cnt[c] == 0;
-                                x.mn[c] = (xfresh || xv < x.mn[c]) ? xv : x.mn[c];
-                                x.mx[c] = (xfresh || xv > x.mx[c]) ? xv : x.mx[c];
-                                x.sm[c] += xv;
-                                x.cnt[c]++;
+                                x.mn[c] = (xok && (xfresh || xv < x.mn[c]))
+                                              ? xv : x.mn[c];
+                                x.mx[c] = (xok && (xfresh || xv > x.mx[c]))
+                                              ? xv : x.mx[c];
+                                x.sm[c] = xok ? x.sm[c] + xv : x.sm[c];
+                                x.cnt[c] += xok ? 1u : 0u;
                             }
                         }
                     }
                 }
+                f_cnt += nv;
             }
         } else {
             /* L1 flush (bin-major staging => coalesced runs); the bin's
