@@ -18,6 +18,7 @@ WINDOW_TUMBLING = 0
 WINDOW_SLIDING = 1
 AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM, AGG_AVG = 0, 1, 2, 3, 4
 AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP, AGG_STDDEV_POP = 5, 6, 7, 8
+AGG_MEDIAN = 16
 VAR_AGGS = frozenset((AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP,
                       AGG_STDDEV_POP))
 KEY_UTF8, KEY_INT64, KEY_DENSE_INT64 = 0, 1, 2
@@ -28,7 +29,9 @@ AGG_BY_NAME = {"count": AGG_COUNT, "min": AGG_MIN, "max": AGG_MAX,
                "var_samp": AGG_VAR_SAMP, "var_sample": AGG_VAR_SAMP,
                "var": AGG_VAR_SAMP, "var_pop": AGG_VAR_POP,
                "stddev": AGG_STDDEV_SAMP, "stddev_samp": AGG_STDDEV_SAMP,
-               "stddev_pop": AGG_STDDEV_POP}
+               "stddev_pop": AGG_STDDEV_POP,
+               # exact median: no _valid companion, it follows "valid"
+               "median": AGG_MEDIAN}
 
 
 class DzAggDesc(ctypes.Structure):
@@ -176,6 +179,12 @@ def lib():
             L.dz_debug_var_finalize.argtypes = [
                 ctypes.c_int32, ctypes.c_uint64, ctypes.c_double,
                 ctypes.POINTER(ctypes.c_double)]
+        except AttributeError:  # older engine build (A/B hook)
+            pass
+        try:
+            L.dz_debug_median_caps.restype = None
+            L.dz_debug_median_caps.argtypes = [
+                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)]
         except AttributeError:  # older engine build (A/B hook)
             pass
         try:
@@ -535,7 +544,8 @@ class WindowOp:
 
     def kernel_stats(self):
         # 32 slots: the stat map currently holds up to 21 entries (6 device
-        # kernels + 10 host timers + 5 emission route counters) — headroom
+        # kernels + 10 host timers + 5 emission route counters; a median op
+        # adds 5 kernels + 1 host timer = 27) — headroom
         # so a new timer can never silently push the roofline's dominant
         # kernel out of the window
         arr = (DzKernelStat * 32)()
@@ -727,6 +737,14 @@ def generate_utf8(device, seed, start_row, n_rows, n_keys, d_lens=None,
     if L.dz_generate_utf8(device, seed, start_row, n_rows, n_keys, d_lens,
                           d_offsets, d_key_data) != DZ_OK:
         raise RuntimeError(f"dz_generate_utf8 failed: {_err(L)}")
+
+
+def median_caps():
+    """(lds_vals, log_min_entries) of the median kernels: the largest group
+    selected in LDS and a value log's first allocation (test hook)."""
+    a, b = ctypes.c_int32(), ctypes.c_int64()
+    lib().dz_debug_median_caps(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
 
 
 def synchronize(device=0):

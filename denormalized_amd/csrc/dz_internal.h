@@ -304,6 +304,50 @@ void launch_egather_slabs_x(hipStream_t stream, const uint64_t* s_base,
                             EGatherSlots slots, int gcount, uint64_t* out);
 void launch_arm_scalars(hipStream_t stream, uint64_t* scalars);
 
+/* Median (kernels.hip §MEDIAN). A window slot's value log is SoA — f64 values
+ * then u32 dense key ids, 12 B per entry of capacity — grown by the host from
+ * exact per-batch counts. MED_LDS_VALS splits k_med_select's two paths: a
+ * group of at most that many values is selected in LDS (16 KiB of keys per
+ * 256-thread block keeps 8 blocks = 32 waves per CU), a longer one over
+ * global memory. MED_LOG_MIN is the first allocation of a log, in entries. */
+constexpr int MED_LDS_VALS = 2048;
+constexpr int64_t MED_LOG_MIN = 4096;
+constexpr int64_t MED_LOG_MAX = (1LL << 31) - 1; /* entries: u32 positions */
+struct MedWin {      /* one window of the batch, indexed by widx */
+    double* val;     /* the slot's log */
+    uint32_t* kid;
+    uint32_t base;   /* entries before this batch */
+    uint32_t cap;    /* capacity (bounds guard) */
+};
+/* per-window valid-row counts of the batch into d_wcnt[nw] (pre-zeroed) */
+void launch_med_count(hipStream_t stream, const int64_t* d_ts,
+                      const uint8_t* d_validity /*bitmap|null*/, int64_t n,
+                      const WinParams& wp, uint32_t* d_wcnt);
+/* append every valid row to each containing window's log; d_fill[nw] is the
+ * batch's per-window cursor (pre-zeroed); overflow flags d_dbg[2] */
+void launch_med_append(hipStream_t stream, const int64_t* d_ts,
+                       const uint8_t* d_validity, const int32_t* d_kid,
+                       const double* d_vals, int64_t n, const WinParams& wp,
+                       const MedWin* d_win, uint32_t* d_fill, uint32_t* d_dbg);
+/* close chain of one slot: d_seg_off[k] = exclusive scan of d_cnt[0..K),
+ * d_fill[0..K) zeroed (d_bsum: ceil(K / 2048) cells of scratch); the log's
+ * values scattered into their segments of d_sorted; med[k] per group */
+void launch_med_scan(hipStream_t stream, const uint64_t* d_cnt, int64_t K,
+                     uint32_t* d_bsum, uint32_t* d_seg_off, uint32_t* d_fill);
+void launch_med_place(hipStream_t stream, const uint32_t* d_lkid,
+                      const double* d_lval, int64_t len,
+                      const uint32_t* d_seg_off, uint32_t* d_fill, int64_t K,
+                      double* d_sorted, uint32_t* d_dbg);
+void launch_med_select(hipStream_t stream, const uint64_t* d_cnt,
+                       const uint32_t* d_seg_off, const double* d_sorted,
+                       int64_t len, int64_t K, double* d_med, uint32_t* d_dbg);
+/* (6 or 7) * kcap cells per close: the 5-field slab, m2 when v_base != null,
+ * then the close's median column d_med[close][kcap] */
+void launch_egather_slabs_med(hipStream_t stream, const uint64_t* s_base,
+                              const double* v_base, const double* d_med,
+                              int64_t kcap, EGatherSlots slots, int gcount,
+                              uint64_t* out);
+
 void launch_fill_i64(hipStream_t stream, int64_t* d_p, int64_t n, int64_t v);
 
 /* JSON ingest (kernels.hip §JSON ingest): newline count/scan, then

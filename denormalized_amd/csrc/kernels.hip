@@ -3300,4 +3300,443 @@ void launch_emission_group_sort(hipStream_t s, int64_t elem_cap, int gcount,
                        gkid, gcnt_col, gmin, gmax, gsum, gavg, gflags, pout);
 }
 
+/* ------------------------------------------------------------------ */
+/* MEDIAN (DZ_AGG_MEDIAN): per-slot value log + order statistic at     */
+/* close                                           */
+/* ------------------------------------------------------------------ */
+/* An exact median cannot fold into registers: every valid value of an open
+ * window is appended to its slot's log as (dense key id, value), and at
+ * close the log is scattered into per-group segments and one block per
+ * group radix-selects the middle order statistic(s). The median does not
+ * depend on row order, so placement uses atomics and stays bit-exact. */
+
+constexpr int MED_TILE = 2048;             /* rows per count/append block */
+constexpr int MED_RPT = MED_TILE / BLOCK;  /* rows one thread holds */
+
+/* The windows of this block's row tile: each thread's rows keep (first widx,
+ * multiplicity) in registers — the same membership rule as k_hist/k_scatter
+ * (row_windows), multiplicity 0 for NULL rows — and the block's touched
+ * widx range [*wlo, *wlo + *span) comes back through s_range. */
+__device__ __forceinline__ void med_tile_windows(
+        const int64_t* __restrict__ ts, const uint8_t* __restrict__ validity,
+        int64_t n, const WinParams& wp, int32_t (&jm)[MED_RPT],
+        int32_t (&m)[MED_RPT], int32_t* s_range, int32_t* wlo, int32_t* span) {
+    if (threadIdx.x == 0) {
+        s_range[0] = INT32_MAX;
+        s_range[1] = -1;
+    }
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * MED_TILE;
+    int32_t lo = INT32_MAX, hi = -1;
+#pragma unroll
+    for (int k = 0; k < MED_RPT; k++) {
+        const int64_t i = base + k * BLOCK + threadIdx.x;
+        jm[k] = 0;
+        m[k] = 0;
+        if (i < n && (!validity || ((validity[i >> 3] >> (i & 7)) & 1))) {
+            int32_t j, mm;
+            row_windows(ts[i], wp, &j, &mm);
+            if (mm > 0 && j >= 0 && j + mm <= wp.nw) {
+                jm[k] = j;
+                m[k] = mm;
+                lo = min(lo, j);
+                hi = max(hi, j + mm - 1);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_down(lo, o));
+        hi = max(hi, __shfl_down(hi, o));
+    }
+    if ((threadIdx.x & 63) == 0 && hi >= 0) {
+        atomicMin(&s_range[0], lo);
+        atomicMax(&s_range[1], hi);
+    }
+    __syncthreads();
+    *wlo = s_range[0];
+    *span = s_range[1] >= s_range[0] ? s_range[1] - s_range[0] + 1 : 0;
+}
+
+/* valid rows of this batch per window: LDS counters over the block's widx
+ * range, then ONE global atomic per (block, touched window) */
+__global__ __launch_bounds__(BLOCK) void k_med_count(
+        const int64_t* __restrict__ ts, const uint8_t* __restrict__ validity,
+        int64_t n, WinParams wp, uint32_t* __restrict__ wcnt) {
+    __shared__ uint32_t lcnt[MAX_RANGES];
+    __shared__ int32_t s_range[2];
+    int32_t jm[MED_RPT], m[MED_RPT], wlo, span;
+    med_tile_windows(ts, validity, n, wp, jm, m, s_range, &wlo, &span);
+    for (int t = threadIdx.x; t < span; t += BLOCK) lcnt[t] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < MED_RPT; k++)
+        for (int32_t j = 0; j < m[k]; j++)
+            atomicAdd(&lcnt[jm[k] - wlo + j], 1u);
+    __syncthreads();
+    for (int t = threadIdx.x; t < span; t += BLOCK) {
+        const uint32_t c = lcnt[t];
+        if (c) atomicAdd(&wcnt[wlo + t], c);
+    }
+}
+
+/* append (key id, value) of every valid row to the log of each window that
+ * contains it: the block reserves one range per touched window with a single
+ * global atomic on the batch's per-window fill counter; positions inside the
+ * range come from LDS atomics. win[w].base is the log length before this
+ * batch (host-tracked, exact), win[w].cap its capacity — the bounds guard. */
+__global__ __launch_bounds__(BLOCK) void k_med_append(
+        const int64_t* __restrict__ ts, const uint8_t* __restrict__ validity,
+        const int32_t* __restrict__ kid, const double* __restrict__ vals,
+        int64_t n, WinParams wp, const MedWin* __restrict__ win,
+        uint32_t* __restrict__ fill, uint32_t* __restrict__ dbg) {
+    __shared__ uint32_t lcnt[MAX_RANGES];
+    __shared__ int32_t s_range[2];
+    int32_t jm[MED_RPT], m[MED_RPT], wlo, span;
+    med_tile_windows(ts, validity, n, wp, jm, m, s_range, &wlo, &span);
+    for (int t = threadIdx.x; t < span; t += BLOCK) lcnt[t] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < MED_RPT; k++)
+        for (int32_t j = 0; j < m[k]; j++)
+            atomicAdd(&lcnt[jm[k] - wlo + j], 1u);
+    __syncthreads();
+    /* the cell turns from the block's count into its reserved start */
+    for (int t = threadIdx.x; t < span; t += BLOCK) {
+        const uint32_t c = lcnt[t];
+        lcnt[t] = c ? atomicAdd(&fill[wlo + t], c) : 0u;
+    }
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * MED_TILE;
+#pragma unroll
+    for (int k = 0; k < MED_RPT; k++) {
+        if (m[k] == 0) continue;
+        const int64_t i = base + k * BLOCK + threadIdx.x;
+        const uint32_t kd = (uint32_t)kid[i];
+        const double v = vals[i];
+        for (int32_t j = 0; j < m[k]; j++) {
+            const int32_t w = jm[k] + j;
+            const uint32_t r = atomicAdd(&lcnt[w - wlo], 1u);
+            const MedWin mw = win[w];
+            const uint64_t pos = (uint64_t)mw.base + r;
+            if (pos < mw.cap) {
+                mw.kid[pos] = kd;
+                mw.val[pos] = v;
+            } else {
+                dbg[2] = 1; /* bounds guard: flag, never corrupt */
+            }
+        }
+    }
+}
+
+void launch_med_count(hipStream_t s, const int64_t* d_ts,
+                      const uint8_t* d_validity, int64_t n,
+                      const WinParams& wp, uint32_t* d_wcnt) {
+    const int grid = (int)((n + MED_TILE - 1) / MED_TILE);
+    hipLaunchKernelGGL(k_med_count, dim3(grid), dim3(BLOCK), 0, s, d_ts,
+                       d_validity, n, wp, d_wcnt);
+}
+
+void launch_med_append(hipStream_t s, const int64_t* d_ts,
+                       const uint8_t* d_validity, const int32_t* d_kid,
+                       const double* d_vals, int64_t n, const WinParams& wp,
+                       const MedWin* d_win, uint32_t* d_fill,
+                       uint32_t* d_dbg) {
+    const int grid = (int)((n + MED_TILE - 1) / MED_TILE);
+    hipLaunchKernelGGL(k_med_append, dim3(grid), dim3(BLOCK), 0, s, d_ts,
+                       d_validity, d_kid, d_vals, n, wp, d_win, d_fill, d_dbg);
+}
+
+/* segment offsets of a closing slot: exclusive scan of its per-group valid
+ * counts (the primary column's s_cnt is exactly each group's segment
+ * length). Three kernels, MED_SCAN_ELEMS groups per block: block sums, a
+ * single-block scan of those, then the offsets — which also zeroes the
+ * per-group fill cursors of k_med_place. */
+constexpr int MED_SCAN_ELEMS = 2048;
+constexpr int MED_SCAN_PT = MED_SCAN_ELEMS / BLOCK;
+
+__global__ __launch_bounds__(BLOCK) void k_med_scan_a(
+        const uint64_t* __restrict__ cnt, int64_t K,
+        uint32_t* __restrict__ bsum) {
+    __shared__ uint32_t wtot[WAVES_PER_BLOCK];
+    const int64_t base =
+        (int64_t)blockIdx.x * MED_SCAN_ELEMS + threadIdx.x * MED_SCAN_PT;
+    uint32_t s = 0;
+#pragma unroll
+    for (int e = 0; e < MED_SCAN_PT; e++)
+        if (base + e < K) s += (uint32_t)cnt[base + e];
+    uint32_t tot;
+    block_scan_excl(s, wtot, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_med_scan_b(
+        uint32_t* __restrict__ bsum, int nblk) {
+    __shared__ uint32_t wtot[WAVES_PER_BLOCK];
+    uint32_t carry = 0;
+    for (int b0 = 0; b0 < nblk; b0 += BLOCK) {
+        const int b = b0 + threadIdx.x;
+        const uint32_t v = b < nblk ? bsum[b] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_scan_excl(v, wtot, &tot);
+        if (b < nblk) bsum[b] = carry + ex;
+        carry += tot;
+        __syncthreads(); /* wtot is rewritten by the next round */
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_med_scan_c(
+        const uint64_t* __restrict__ cnt, int64_t K,
+        const uint32_t* __restrict__ bsum, uint32_t* __restrict__ seg_off,
+        uint32_t* __restrict__ fill) {
+    __shared__ uint32_t wtot[WAVES_PER_BLOCK];
+    const int64_t base =
+        (int64_t)blockIdx.x * MED_SCAN_ELEMS + threadIdx.x * MED_SCAN_PT;
+    uint32_t c[MED_SCAN_PT];
+    uint32_t s = 0;
+#pragma unroll
+    for (int e = 0; e < MED_SCAN_PT; e++) {
+        c[e] = base + e < K ? (uint32_t)cnt[base + e] : 0u;
+        s += c[e];
+    }
+    uint32_t tot;
+    uint32_t ex = block_scan_excl(s, wtot, &tot) + bsum[blockIdx.x];
+#pragma unroll
+    for (int e = 0; e < MED_SCAN_PT; e++) {
+        if (base + e < K) {
+            seg_off[base + e] = ex;
+            fill[base + e] = 0;
+        }
+        ex += c[e];
+    }
+}
+
+void launch_med_scan(hipStream_t s, const uint64_t* d_cnt, int64_t K,
+                     uint32_t* d_bsum, uint32_t* d_seg_off, uint32_t* d_fill) {
+    const int nblk = (int)((K + MED_SCAN_ELEMS - 1) / MED_SCAN_ELEMS);
+    if (nblk < 1) return;
+    hipLaunchKernelGGL(k_med_scan_a, dim3(nblk), dim3(BLOCK), 0, s, d_cnt, K,
+                       d_bsum);
+    hipLaunchKernelGGL(k_med_scan_b, dim3(1), dim3(BLOCK), 0, s, d_bsum, nblk);
+    hipLaunchKernelGGL(k_med_scan_c, dim3(nblk), dim3(BLOCK), 0, s, d_cnt, K,
+                       d_bsum, d_seg_off, d_fill);
+}
+
+/* scatter the log's values into their groups' segments, one thread per
+ * entry: destination = seg_off[kid] + atomicAdd(&fill[kid], 1) — the order
+ * inside a segment is irrelevant to an order statistic. A wave whose entries
+ * all share one key (a global window; long runs of one sensor) reserves its
+ * range with one atomic. Guards (dbg[2]): a key id outside [0, K) or a
+ * destination outside the slot's `len` entries is skipped and flagged. */
+__global__ __launch_bounds__(BLOCK) void k_med_place(
+        const uint32_t* __restrict__ lkid, const double* __restrict__ lval,
+        uint32_t len, const uint32_t* __restrict__ seg_off,
+        uint32_t* __restrict__ fill, uint32_t K, double* __restrict__ sorted,
+        uint32_t* __restrict__ dbg) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool act = i < len;
+    const uint32_t kd = act ? lkid[i] : 0xFFFFFFFFu;
+    const bool ok = act && kd < K;
+    if (act && !ok) dbg[2] = 2;
+    const uint64_t am = __ballot(ok);
+    if (!am) return; /* wave-uniform */
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)am) - 1;
+    const uint32_t k0 = (uint32_t)__shfl((int)kd, leader);
+    uint32_t r = 0;
+    if (__ballot(ok && kd != k0) == 0) {
+        uint32_t b = 0;
+        if (lane == leader) b = atomicAdd(&fill[k0], (uint32_t)__popcll(am));
+        b = (uint32_t)__shfl((int)b, leader);
+        r = b + (uint32_t)__popcll(am & ((1ULL << lane) - 1));
+    } else if (ok) {
+        r = atomicAdd(&fill[kd], 1u);
+    }
+    if (ok) {
+        const uint64_t dst = (uint64_t)seg_off[kd] + r;
+        if (dst < len) sorted[dst] = lval[i];
+        else dbg[2] = 3;
+    }
+}
+
+void launch_med_place(hipStream_t s, const uint32_t* d_lkid,
+                      const double* d_lval, int64_t len,
+                      const uint32_t* d_seg_off, uint32_t* d_fill, int64_t K,
+                      double* d_sorted, uint32_t* d_dbg) {
+    if (len <= 0) return;
+    const int grid = (int)((len + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_med_place, dim3(grid), dim3(BLOCK), 0, s, d_lkid,
+                       d_lval, (uint32_t)len, d_seg_off, d_fill, (uint32_t)K,
+                       d_sorted, d_dbg);
+}
+
+/* IEEE total order as an unsigned key (-NaN < -inf < ... < -0 < +0 < ... <
+ * +inf < +NaN): bits ^ (sign ? ~0 : 1 << 63), and back */
+__device__ __forceinline__ uint64_t med_key(double v) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    return b ^ ((b >> 63) ? ~0ULL : 0x8000000000000000ULL);
+}
+__device__ __forceinline__ double med_unkey(uint64_t k) {
+    const uint64_t b = (k >> 63) ? (k ^ 0x8000000000000000ULL) : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+/* One block per group: MSD radix select (8 passes of 8 bits) on the 64-bit
+ * total-order key for rank (n-1)/2. Each pass histograms the digit of the
+ * candidates that still match the selected prefix, scans the 256 bins across
+ * the block and narrows to the bin holding the rank; the running count of
+ * keys below the prefix and the final bin's size say, for even n, whether
+ * rank n/2 is the same value (ties) — otherwise it is the minimum of the
+ * keys above, one more pass. Segments of at most MED_LDS_VALS values are
+ * loaded ONCE into LDS as keys and selected there; longer ones run the same
+ * passes over global memory. A wave whose candidates all carry one digit
+ * (common: the high bytes of same-magnitude readings) adds its count with a
+ * single LDS atomic.
+ * LDS: 16 KiB keys + 1 KiB bins => 9 blocks/CU by LDS, 8 by the 32-wave
+ * cap: full occupancy at BLOCK = 256 (DESIGN.md §Median has the figures). */
+static_assert(BLOCK == 256, "k_med_select scans one digit bin per thread");
+__global__ __launch_bounds__(BLOCK) void k_med_select(
+        const uint64_t* __restrict__ cnt, const uint32_t* __restrict__ seg_off,
+        const double* __restrict__ sorted, uint32_t len,
+        double* __restrict__ med, uint32_t* __restrict__ dbg) {
+    __shared__ uint64_t keys[MED_LDS_VALS];
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t wtot[WAVES_PER_BLOCK];
+    __shared__ uint32_t s_sel[3]; /* digit, rank inside its bin, bin size */
+    __shared__ unsigned long long s_min;
+    const uint32_t k = blockIdx.x;
+    const uint64_t n64 = cnt[k];
+    if (n64 == 0) { /* block-uniform: NULL group, the host emits 0.0 */
+        if (threadIdx.x == 0) med[k] = 0.0;
+        return;
+    }
+    const uint32_t off = seg_off[k];
+    if ((uint64_t)off + n64 > len) { /* bounds guard: flag, never read past */
+        if (threadIdx.x == 0) {
+            med[k] = 0.0;
+            dbg[2] = 4;
+        }
+        return;
+    }
+    const uint32_t n = (uint32_t)n64;
+    const double* __restrict__ seg = sorted + off;
+    const bool in_lds = n <= (uint32_t)MED_LDS_VALS;
+    const int lane = threadIdx.x & 63;
+    if (in_lds) {
+        for (uint32_t i = threadIdx.x; i < n; i += BLOCK)
+            keys[i] = med_key(seg[i]);
+    }
+    if (threadIdx.x == 0) s_min = ~0ULL;
+    __syncthreads();
+    uint64_t prefix = 0, mask = 0;
+    uint32_t r = (n - 1) / 2; /* rank still to find among the candidates */
+    uint32_t below = 0;       /* keys strictly below the prefix */
+    uint32_t eq = n;          /* candidates matching the prefix */
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t b0 = 0; b0 < n; b0 += BLOCK) {
+            const uint32_t i = b0 + threadIdx.x;
+            bool hit = false;
+            uint32_t d = 0;
+            if (i < n) {
+                const uint64_t key = in_lds ? keys[i] : med_key(seg[i]);
+                hit = (key & mask) == prefix;
+                d = (uint32_t)(key >> shift) & 255u;
+            }
+            const uint64_t hm = __ballot(hit);
+            if (hm) {
+                const int leader = __ffsll((long long)hm) - 1;
+                const uint32_t d0 = (uint32_t)__shfl((int)d, leader);
+                if (__ballot(hit && d != d0) == 0) {
+                    if (lane == leader)
+                        atomicAdd(&hist[d0], (uint32_t)__popcll(hm));
+                } else if (hit) {
+                    atomicAdd(&hist[d], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t c = hist[threadIdx.x];
+        uint32_t tot;
+        const uint32_t ex = block_scan_excl(c, wtot, &tot);
+        if (c && ex <= r && r < ex + c) {
+            s_sel[0] = threadIdx.x;
+            s_sel[1] = r - ex;
+            s_sel[2] = c;
+        }
+        __syncthreads();
+        below += r - s_sel[1];
+        r = s_sel[1];
+        eq = s_sel[2];
+        prefix |= (uint64_t)s_sel[0] << shift;
+        mask |= 0xFFULL << shift;
+    }
+    uint64_t hi_key = prefix;
+    if ((n & 1) == 0 && below + eq <= n / 2) {
+        /* block-uniform: rank n/2 is the smallest key above the selected */
+        uint64_t mn = ~0ULL;
+        for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {
+            const uint64_t key = in_lds ? keys[i] : med_key(seg[i]);
+            if (key > prefix && key < mn) mn = key;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t u =
+                (uint64_t)__shfl_down((unsigned long long)mn, o);
+            mn = u < mn ? u : mn;
+        }
+        if (lane == 0) atomicMin(&s_min, (unsigned long long)mn);
+        __syncthreads();
+        hi_key = s_min;
+    }
+    if (threadIdx.x == 0) {
+        const double lo = med_unkey(prefix);
+        /* even n: one f64 add, one f64 divide, each rounded on its own —
+         * also when both middles are equal (1e308 + 1e308 overflows) */
+        med[k] = (n & 1) ? lo : (lo + med_unkey(hi_key)) / 2.0;
+    }
+}
+
+void launch_med_select(hipStream_t s, const uint64_t* d_cnt,
+                       const uint32_t* d_seg_off, const double* d_sorted,
+                       int64_t len, int64_t K, double* d_med,
+                       uint32_t* d_dbg) {
+    if (K <= 0) return;
+    hipLaunchKernelGGL(k_med_select, dim3((uint32_t)K), dim3(BLOCK), 0, s,
+                       d_cnt, d_seg_off, d_sorted, (uint32_t)len, d_med, d_dbg);
+}
+
+/* median-declaring ops: each packed close is the 5-field slab, the slot's m2
+ * column when the op also declares a variance aggregate (v_base != null),
+ * then the close's median column (med is [close][kcap]) */
+__global__ void k_egather_slabs_med(const uint64_t* __restrict__ s_base,
+                                    const uint64_t* __restrict__ v_base,
+                                    const uint64_t* __restrict__ med,
+                                    int64_t kcap, EGatherSlots slots,
+                                    uint64_t* __restrict__ out) {
+    const int g = blockIdx.y;
+    const int64_t slot = slots.s[g];
+    const int64_t nf = v_base ? 7 : 6;
+    const uint64_t* src = s_base + slot * (5 * kcap);
+    const uint64_t* m2 = v_base ? v_base + slot * (2 * kcap) + kcap : nullptr;
+    const uint64_t* md = med + (int64_t)g * kcap;
+    uint64_t* dst = out + (int64_t)g * (nf * kcap);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nf * kcap; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = i < 5 * kcap ? src[i]
+               : (m2 && i < 6 * kcap) ? m2[i - 5 * kcap]
+               : md[i - (nf - 1) * kcap];
+}
+
+void launch_egather_slabs_med(hipStream_t s, const uint64_t* s_base,
+                              const double* v_base, const double* d_med,
+                              int64_t kcap, EGatherSlots slots, int gcount,
+                              uint64_t* out) {
+    const int64_t nf = v_base ? 7 : 6;
+    int bx = (int)std::min<int64_t>((nf * kcap + BLOCK - 1) / BLOCK, 512);
+    dim3 grid(bx, gcount);
+    hipLaunchKernelGGL(k_egather_slabs_med, grid, dim3(BLOCK), 0, s, s_base,
+                       (const uint64_t*)v_base, (const uint64_t*)d_med, kcap,
+                       slots, out);
+}
+
 } // namespace dz

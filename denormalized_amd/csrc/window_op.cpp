@@ -90,6 +90,12 @@ extern "C" int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count,
     return 1;
 }
 
+extern "C" void dz_debug_median_caps(int32_t* lds_vals,
+                                     int64_t* log_min_entries) {
+    if (lds_vals) *lds_vals = dz::MED_LDS_VALS;
+    if (log_min_entries) *log_min_entries = dz::MED_LOG_MIN;
+}
+
 extern "C" const char* dz_version(void) { return "denormalized-amd 0.1 (gfx950)"; }
 
 /* ------------------------------------------------------------------ */
@@ -249,9 +255,48 @@ struct dz_window_op {
     int32_t dcols[1 + dz::MAX_EXTRA_COLS] = {}; /* batch column index */
     std::vector<int32_t> agg_col;  /* per aggregate: 0 primary, 1..nx extra */
     uint64_t* x_slab = nullptr;
-    /* 8-byte cells of one packed close in the pinned group buffers */
-    int64_t close_fields() const { return has_var ? 6 : 5 + 4 * nx; }
-    bool host_route() const { return has_var || nx > 0; }
+    /* median (has_med): every valid row of an open window is appended to the
+     * slot's value log — one device buffer per slot, f64 values then u32
+     * dense key ids (12 B per entry of capacity), capacity kept across slot
+     * reuse. The cursor is `len`, on the host: the append reserves from
+     * exact per-batch counts the host has read back, so it always knows it;
+     * it returns to zero where the slot enters the reset list. At close the
+     * chain scan -> place -> select leaves med[close][kcap] in d_med_out,
+     * which travels as one more column of the packed close. Nothing below
+     * is allocated and no median kernel is launched while has_med is false.
+     * Median ops emit through the host-built path at every key count. */
+    bool has_med = false;
+    struct MedLog {
+        char* base = nullptr;
+        int64_t cap = 0, len = 0; /* entries */
+        double* vals() const { return (double*)base; }
+        uint32_t* kids() const { return (uint32_t*)(base + cap * 8); }
+    };
+    std::vector<MedLog> med_logs;     /* by slot */
+    uint32_t* d_med_wcnt = nullptr;   /* 2 x MAX_RANGES: counts, fill cursors */
+    uint32_t* h_med_wcnt = nullptr;   /* pinned readback of the counts */
+    dz::MedWin* d_med_win = nullptr;  /* MAX_RANGES, by widx */
+    dz::MedWin* h_med_win = nullptr;  /* pinned upload staging: rewritten only
+                                       * after the next batch's count wait,
+                                       * which the previous upload precedes
+                                       * on the compute stream */
+    hipEvent_t med_ev = nullptr;      /* the count readback is host-visible */
+    /* close-chain scratch, used on copy_stream only (in-stream order makes
+     * it reusable from one close to the next) */
+    uint32_t* d_med_segoff = nullptr; /* kcap */
+    uint32_t* d_med_fill = nullptr;   /* kcap */
+    uint32_t* d_med_bsum = nullptr;
+    double* d_med_out = nullptr;      /* E_POOL / 2 closes x kcap */
+    int64_t med_scratch_kcap = 0;
+    double* d_med_sorted = nullptr;   /* the closing slot's placed values */
+    int64_t med_sorted_cap = 0;
+    /* 8-byte cells of one packed close in the pinned group buffers: the
+     * 5-field slab, then m2 (has_var), the median (has_med) or the extras'
+     * 4 * nx fields (never together with the other two) */
+    int64_t close_fields() const {
+        return 5 + (has_var ? 1 : 0) + (has_med ? 1 : 0) + 4 * nx;
+    }
+    bool host_route() const { return has_var || has_med || nx > 0; }
     struct XCols { /* one push's extra columns (device pointers) */
         const double* vals[dz::MAX_EXTRA_COLS] = {};
         const uint8_t* valid[dz::MAX_EXTRA_COLS] = {};
@@ -709,15 +754,16 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
         return nullptr;
     }
     if (desc->n_aggs <= 0 || !desc->aggs) { g_err = "need at least one aggregate"; return nullptr; }
-    bool any_var = false;
+    bool any_var = false, any_med = false;
     for (int32_t a = 0; a < desc->n_aggs; a++) {
         const int32_t o = (int32_t)desc->aggs[a].op;
-        if (o < DZ_AGG_COUNT || o > DZ_AGG_STDDEV_POP) {
+        if ((o < DZ_AGG_COUNT || o > DZ_AGG_STDDEV_POP) && o != DZ_AGG_MEDIAN) {
             g_err = "aggregate " + std::to_string(a) + ": unknown op code " +
-                    std::to_string(o) + " (valid: 0..8, see dz_agg_op)";
+                    std::to_string(o) + " (valid: 0..8 and 16, see dz_agg_op)";
             return nullptr;
         }
         any_var = any_var || is_var_op(o);
+        any_med = any_med || o == DZ_AGG_MEDIAN;
     }
     /* distinct input columns, numbered in order of first appearance */
     int32_t dcols[1 + dz::MAX_EXTRA_COLS];
@@ -742,6 +788,11 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
                 "(several value columns are not supported with them)";
         return nullptr;
     }
+    if (any_med && ndc > 1) {
+        g_err = "median aggregates need a single input column "
+                "(several value columns are not supported with them)";
+        return nullptr;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= desc->device) {
         g_err = "no HIP device available (this operator has no CPU fallback)";
@@ -757,6 +808,7 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
     op->key_kind = op->no_group ? DZ_KEY_DENSE_INT64 : desc->key_kind;
     op->aggs.assign(desc->aggs, desc->aggs + desc->n_aggs);
     op->has_var = any_var;
+    op->has_med = any_med;
     op->nx = ndc - 1;
     memcpy(op->dcols, dcols, sizeof(dcols[0]) * ndc);
     op->agg_col = agg_col;
@@ -801,6 +853,14 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
         hipEventCreateWithFlags(&op->ev_ready[i], hipEventDisableTiming);
         hipEventCreateWithFlags(&op->ev_staged[i], hipEventDisableTiming);
         hipEventCreateWithFlags(&op->ev_consumed[i], hipEventDisableTiming);
+    }
+    if (op->has_med) {
+        hipMalloc(&op->d_med_wcnt, (size_t)2 * dz::MAX_RANGES * 4);
+        hipMalloc(&op->d_med_win, (size_t)dz::MAX_RANGES * sizeof(dz::MedWin));
+        hipHostMalloc((void**)&op->h_med_wcnt, (size_t)dz::MAX_RANGES * 4);
+        hipHostMalloc((void**)&op->h_med_win,
+                      (size_t)dz::MAX_RANGES * sizeof(dz::MedWin));
+        hipEventCreateWithFlags(&op->med_ev, hipEventDisableTiming);
     }
     int64_t hint = std::max<int64_t>(desc->n_keys_hint, 1);
     if (state_alloc(op, hint, 4) != DZ_OK) {
@@ -857,6 +917,14 @@ extern "C" void dz_window_op_destroy(dz_window_op* op) {
     hipFree(op->s_base);
     hipFree(op->v_base);
     hipFree(op->x_slab);
+    for (auto& lg : op->med_logs) hipFree(lg.base);
+    hipFree(op->d_med_wcnt); hipFree(op->d_med_win);
+    hipFree(op->d_med_segoff); hipFree(op->d_med_fill);
+    hipFree(op->d_med_bsum); hipFree(op->d_med_out);
+    hipFree(op->d_med_sorted);
+    if (op->h_med_wcnt) hipHostFree(op->h_med_wcnt);
+    if (op->h_med_win) hipHostFree(op->h_med_win);
+    if (op->med_ev) hipEventDestroy(op->med_ev);
     for (int c = 0; c < dz::MAX_EXTRA_COLS; c++) {
         hipFree(op->d_xvals[c]);
         hipFree(op->d_xbm[c]);
@@ -913,11 +981,12 @@ extern "C" const char* dz_last_error(dz_window_op* op) {
 
 
 static bool filter_pass(dz_window_op* op, uint64_t row_cnt,
-                        double vmin, double vmax, double vsum, double vm2) {
+                        double vmin, double vmax, double vsum, double vm2,
+                        double vmed) {
     const dz::EmitFilter& ef = op->filter;
     if (!ef.on) return true;
     dz_agg_op o = op->aggs[op->f_idx].op;
-    if (!is_var_op(o)) {
+    if (!is_var_op(o) && o != DZ_AGG_MEDIAN) {
         /* a comparator code outside 0..5 passes every non-NULL group here,
          * while the device chains compare it as != (emit_filter_pass's
          * default arm): both long-standing, kept apart on purpose */
@@ -926,7 +995,12 @@ static bool filter_pass(dz_window_op* op, uint64_t row_cnt,
     }
     /* the comparison runs on the finalised value; NULL never passes */
     double v;
-    if (dz_debug_var_finalize(o, row_cnt, vm2, &v) != 1) return false;
+    if (o == DZ_AGG_MEDIAN) {
+        if (row_cnt == 0) return false;
+        v = vmed;
+    } else if (dz_debug_var_finalize(o, row_cnt, vm2, &v) != 1) {
+        return false;
+    }
     switch (ef.cmp) {
         case 0: return v < ef.lit;
         case 1: return v <= ef.lit;
@@ -985,6 +1059,9 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const double* f_sum = (const double*)(slab + 4 * kcap);
     const double* f_m2 =
         op->has_var ? (const double*)(slab + 5 * kcap) : nullptr;
+    /* median-declaring ops: the close's median column is the last field */
+    const double* f_med = op->has_med
+        ? (const double*)(slab + (op->close_fields() - 1) * kcap) : nullptr;
     /* multi-column ops: column c's (cnt, min, max, sum) — the main slab's for
      * the primary, fields 5 + 4 (c - 1) .. of the packed close for extra c */
     const uint64_t* c_cnt[1 + dz::MAX_EXTRA_COLS] = {f_cnt};
@@ -1031,7 +1108,8 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     for (auto& p : touched) {
         int32_t k = p.second;
         if (filter_pass(op, c_cnt[fc][k], c_min[fc][k], c_max[fc][k],
-                        c_sum[fc][k], f_m2 ? f_m2[k] : 0.0))
+                        c_sum[fc][k], f_m2 ? f_m2[k] : 0.0,
+                        f_med ? f_med[k] : 0.0))
             rows.push_back(k);
     }
     size_t n = rows.size(), na = op->aggs.size();
@@ -1105,6 +1183,13 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                     msk[i] = (uint8_t)dz_debug_var_finalize(
                         op->aggs[a].op, f_cnt[rows[i]], f_m2[rows[i]],
                         &col[i]);
+                break;
+            }
+            case DZ_AGG_MEDIAN: {
+                auto& col = ob.agg_f64[a];
+                col.resize(n);
+                for (size_t i = 0; i < n; i++)
+                    col[i] = f_cnt[rows[i]] ? f_med[rows[i]] : 0.0;
                 break;
             }
         }
@@ -1664,10 +1749,70 @@ static dz_status enqueue_group_device(dz_window_op* op, const Closed* cl,
  * launch into a pinned group buffer behind ONE shared event — the push
  * thread pays a fixed ~4 hip calls per group instead of ~5 per close
  * (measured ~55 µs x ~8 closes/step at cfg2) */
+/* Median close chain of one trigger group, on the copy stream ahead of the
+ * group's gather (the stream already waits for the closing batch's folds and
+ * appends): per closing slot, scan its group counts into segment offsets,
+ * place the log's values into their segments, select one median per group
+ * into d_med_out[close]. The gather reads d_med_out behind it in stream
+ * order, and the frontier event recorded after the gather releases the slot,
+ * so the slot's log is not overwritten before the chain has read it. */
+static dz_status med_close_chain(dz_window_op* op, const Closed* cl,
+                                 int gcount) {
+    hipStream_t cs = op->copy_stream;
+    const int64_t K = op->n_keys;
+    if (op->med_scratch_kcap != op->kcap) {
+        /* earlier chains on this stream may still use the scratch */
+        CHK(op, hipStreamSynchronize(cs));
+        hipFree(op->d_med_segoff); hipFree(op->d_med_fill);
+        hipFree(op->d_med_bsum); hipFree(op->d_med_out);
+        op->d_med_segoff = op->d_med_fill = op->d_med_bsum = nullptr;
+        op->d_med_out = nullptr;
+        op->med_scratch_kcap = 0;
+        CHK(op, hipMalloc(&op->d_med_segoff, (size_t)op->kcap * 4));
+        CHK(op, hipMalloc(&op->d_med_fill, (size_t)op->kcap * 4));
+        CHK(op, hipMalloc(&op->d_med_bsum, ((size_t)op->kcap / 2048 + 1) * 4));
+        CHK(op, hipMalloc(&op->d_med_out,
+                          (size_t)(dz_window_op::E_POOL / 2) * op->kcap * 8));
+        op->med_scratch_kcap = op->kcap;
+    }
+    int64_t max_len = 1;
+    for (int i = 0; i < gcount; i++)
+        max_len = std::max(max_len, op->med_logs[cl[i].slot].len);
+    if (max_len > op->med_sorted_cap) {
+        CHK(op, hipStreamSynchronize(cs));
+        hipFree(op->d_med_sorted);
+        op->d_med_sorted = nullptr;
+        op->med_sorted_cap = 0;
+        CHK(op, hipMalloc(&op->d_med_sorted, (size_t)max_len * 8));
+        op->med_sorted_cap = max_len;
+    }
+    for (int i = 0; i < gcount; i++) {
+        const dz_window_op::MedLog& lg = op->med_logs[cl[i].slot];
+        const uint64_t* cnt = op->s_cnt + (size_t)cl[i].slot * 5 * op->kcap;
+        double* med = op->d_med_out + (size_t)i * op->kcap;
+        timed_on(op, cs, "med_scan", (double)K * 16, [&] {
+            dz::launch_med_scan(cs, cnt, K, op->d_med_bsum, op->d_med_segoff,
+                                op->d_med_fill);
+        });
+        timed_on(op, cs, "med_place", (double)lg.len * 28, [&] {
+            dz::launch_med_place(cs, lg.kids(), lg.vals(), lg.len,
+                                 op->d_med_segoff, op->d_med_fill, K,
+                                 op->d_med_sorted, op->d_dbg);
+        });
+        timed_on(op, cs, "med_select", (double)lg.len * 8 + (double)K * 20,
+                 [&] {
+            dz::launch_med_select(cs, cnt, op->d_med_segoff, op->d_med_sorted,
+                                  lg.len, K, med, op->d_dbg);
+        });
+    }
+    return DZ_OK;
+}
+
 static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
                                     int gcount) {
     hipEvent_t gev;
     int gbuf;
+    if (op->has_med && med_close_chain(op, cl, gcount) != DZ_OK) return DZ_ERR;
     {
         HostTimer htw(op, "h_emit_slabwait");
         std::unique_lock<std::mutex> lk(op->e_mtx);
@@ -1699,7 +1844,12 @@ static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
                           " keys overflows the pinned group buffer";
                 return DZ_ERR;
             }
-            if (op->has_var)
+            if (op->has_med)
+                dz::launch_egather_slabs_med(op->copy_stream, op->s_base,
+                                             op->v_base, op->d_med_out,
+                                             op->kcap, gs, gcount,
+                                             op->e_gbufs_dev[gbuf]);
+            else if (op->has_var)
                 dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
                                              op->v_base, op->kcap, gs, gcount,
                                              op->e_gbufs_dev[gbuf]);
@@ -2094,6 +2244,114 @@ static dz_status stage_core(dz_window_op* op, int64_t n, const int64_t* d_ts,
  * partition + fold, advance the watermark and trigger closes. */
 static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P);
 
+/* Median: append the batch's valid rows to the value logs of the windows
+ * they belong to. Runs after the slotmap upload, on the compute stream:
+ *  1. k_med_count: exact valid-row counts per window of this batch;
+ *  2. one pinned readback and one wait; the host grows every slot log that
+ *     needs it (allocate, copy the old entries, swap, free);
+ *  3. k_med_append writes the entries.
+ * Exact counts, not upper bounds: a sliding batch that spans many windows
+ * would otherwise reserve n entries in each. Freeing an old log is safe
+ * after a compute-stream sync: the stream already waits on the frontier
+ * event that released the slot (taken above, in process_batch), so a close
+ * chain of the slot's previous frame that still read the log has completed
+ * by then — and the wait of step 2 is such a sync. A failed allocation
+ * changes no log: the batch is refused before anything is appended. */
+static dz_status med_append(dz_window_op* op, const dz_window_op::Pend& P,
+                            const dz::WinParams& wp,
+                            const std::vector<int32_t>& slotmap) {
+    const int32_t nw = wp.nw;
+    const int64_t n = P.n;
+    if ((int32_t)op->med_logs.size() < op->nslots)
+        op->med_logs.resize(op->nslots);
+    uint32_t* d_wcnt = op->d_med_wcnt;
+    uint32_t* d_fill = op->d_med_wcnt + dz::MAX_RANGES;
+    CHK(op, hipMemsetAsync(d_wcnt, 0, (size_t)2 * dz::MAX_RANGES * 4,
+                           op->stream));
+    timed(op, "med_count", (double)n * 8, [&] {
+        dz::launch_med_count(op->stream, P.ts, P.valbm, n, wp, d_wcnt);
+    });
+    CHK(op, hipMemcpyAsync(op->h_med_wcnt, d_wcnt, (size_t)nw * 4,
+                           hipMemcpyDeviceToHost, op->stream));
+    CHK(op, hipEventRecord(op->med_ev, op->stream));
+    {
+        HostTimer ht(op, "h_med_wait");
+        event_spin(op->med_ev);
+    }
+    CHK(op, hipEventQuery(op->med_ev)); /* a device fault ends the spin too */
+    /* grow first, touching no log state until every allocation succeeded */
+    struct Grow { int32_t slot; char* base; int64_t cap; };
+    std::vector<Grow> grown;
+    for (int32_t r = 0; r < nw; r++) {
+        const dz_window_op::MedLog& lg = op->med_logs[slotmap[r]];
+        const int64_t need = lg.len + (int64_t)op->h_med_wcnt[r];
+        if (need <= lg.cap) continue;
+        dz_status st = DZ_OK;
+        char* nb = nullptr;
+        int64_t ncap = 0;
+        if (need > dz::MED_LOG_MAX) {
+            op->err = "median: a window would hold " + std::to_string(need) +
+                      " values (limit " + std::to_string(dz::MED_LOG_MAX) + ")";
+            st = DZ_ERR;
+        } else {
+            ncap = std::min(dz::MED_LOG_MAX,
+                            std::max({dz::MED_LOG_MIN, need,
+                                      lg.cap + lg.cap / 2}));
+            hipError_t e = hipMalloc(&nb, (size_t)ncap * 12);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                op->err = "median: cannot allocate a value log of " +
+                          std::to_string(ncap) + " entries (" +
+                          std::to_string(ncap * 12) + " bytes): " +
+                          hipGetErrorString(e);
+                st = DZ_ERR;
+            }
+        }
+        if (st != DZ_OK) {
+            for (auto& g : grown) hipFree(g.base);
+            return DZ_ERR;
+        }
+        grown.push_back({slotmap[r], nb, ncap});
+    }
+    if (!grown.empty()) {
+        std::vector<char*> old;
+        for (auto& g : grown) {
+            dz_window_op::MedLog& lg = op->med_logs[g.slot];
+            dz_window_op::MedLog nl;
+            nl.base = g.base;
+            nl.cap = g.cap;
+            nl.len = lg.len;
+            if (lg.len > 0) {
+                CHK(op, hipMemcpyAsync(nl.vals(), lg.vals(), (size_t)lg.len * 8,
+                                       hipMemcpyDeviceToDevice, op->stream));
+                CHK(op, hipMemcpyAsync(nl.kids(), lg.kids(), (size_t)lg.len * 4,
+                                       hipMemcpyDeviceToDevice, op->stream));
+            }
+            if (lg.base) old.push_back(lg.base);
+            lg = nl;
+        }
+        CHK(op, hipStreamSynchronize(op->stream));
+        for (char* p : old) hipFree(p);
+    }
+    for (int32_t r = 0; r < nw; r++) {
+        dz_window_op::MedLog& lg = op->med_logs[slotmap[r]];
+        dz::MedWin& mw = op->h_med_win[r];
+        mw.val = lg.vals();
+        mw.kid = lg.kids();
+        mw.base = (uint32_t)lg.len;
+        mw.cap = (uint32_t)lg.cap;
+        lg.len += (int64_t)op->h_med_wcnt[r];
+    }
+    CHK(op, hipMemcpyAsync(op->d_med_win, op->h_med_win,
+                           (size_t)nw * sizeof(dz::MedWin),
+                           hipMemcpyHostToDevice, op->stream));
+    timed(op, "med_append", (double)n * 36, [&] {
+        dz::launch_med_append(op->stream, P.ts, P.valbm, P.kid, P.vals, n, wp,
+                              op->d_med_win, d_fill, op->d_dbg);
+    });
+    return DZ_OK;
+}
+
 static dz_status process_pending(dz_window_op* op) {
     if (!op->pend.active) return DZ_OK;
     CHK(op, hipSetDevice(op->device));
@@ -2190,6 +2448,11 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                 }
             }
             reset_list.push_back(fs.slot);
+            if (op->has_med) { /* a fresh frame starts an empty log */
+                if ((int32_t)op->med_logs.size() < op->nslots)
+                    op->med_logs.resize(op->nslots);
+                op->med_logs[fs.slot].len = 0;
+            }
             op->open[ws[r]] = {we[r], fs.slot, op->rows_seen};
             slotmap[r] = fs.slot;
         } else {
@@ -2218,6 +2481,12 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
 
     wp.s0 = nw > 0 ? ws[0] : 0;
     wp.nw = (int32_t)nw;
+
+    /* median: log this batch's valid rows, once per batch over the FULL
+     * window range — the log does not depend on the fold regime below */
+    if (op->has_med && nw > 0 &&
+        med_append(op, P, wp, slotmap) != DZ_OK)
+        return DZ_ERR;
 
     /* 3. partition + fold */
     int64_t expand = sliding

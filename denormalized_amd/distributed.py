@@ -10,9 +10,10 @@ rank-major, matching the reference's partition-merge structure rather than
 single-stream row order — see DESIGN.md)."""
 import numpy as np
 
-from ._lib import AGG_BY_NAME, VAR_AGGS
+from ._lib import AGG_BY_NAME, AGG_MEDIAN, VAR_AGGS
 
 _VAR_NAMES = frozenset(n for n, code in AGG_BY_NAME.items() if code in VAR_AGGS)
+_MED_NAMES = frozenset(n for n, code in AGG_BY_NAME.items() if code == AGG_MEDIAN)
 
 
 def merge_global_partials(per_rank_batches):
@@ -27,6 +28,12 @@ def merge_global_partials(per_rank_batches):
                     f"merge_global_partials cannot merge {bad}: combining "
                     "Welford (count, mean, m2) partials needs a different "
                     "formula than count/min/max/sum and is not supported")
+            bad = sorted(k for k in b if k in _MED_NAMES)
+            if bad:
+                raise ValueError(
+                    f"merge_global_partials cannot merge {bad}: a median "
+                    "does not combine from per-rank partials (it needs every "
+                    "value of the window) and is not supported")
             # an aggregate on an extra value column reports its own mask as
             # "<name>_valid": such batches carry several columns' partials
             extra = sorted(k for k in b if k.endswith("_valid")

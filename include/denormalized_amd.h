@@ -54,6 +54,29 @@ typedef enum dz_agg_op {
     DZ_AGG_VAR_POP     = 6,
     DZ_AGG_STDDEV_SAMP = 7,
     DZ_AGG_STDDEV_POP  = 8,
+    /* Exact median (the reference's median, functions.py:1768; the same
+     * example declares it, stream_aggregate.py:52). Codes 9..15 are not
+     * assigned and are refused. Per (window, key) group: the column's valid
+     * values sorted by IEEE total order (-NaN < -inf < ... < -0.0 < +0.0 <
+     * ... < +inf < +NaN; sort key = bits ^ (sign ? ~0 : 1 << 63)); n == 0:
+     * NULL; n odd: v[n/2]; n even: (v[n/2-1] + v[n/2]) / 2.0 — one f64 add
+     * and one f64 divide, each rounded on its own, so an overflow to +-inf
+     * and inf + -inf = NaN come out as they are. Row order does not matter.
+     * An f64 column whose NULL-ness is agg_valid's (its agg_valid_cols entry
+     * is NULL). A median op may also declare count/min/max/sum/avg and the
+     * variance family on the same column; dz_window_op_create refuses it
+     * with more than one distinct value column. Median ops build every
+     * emitted batch on the host, at every key count.
+     * MEMORY: every valid row is kept, per window it belongs to (a sliding
+     * row: every window containing it), until that window closes: 12 B per
+     * entry of capacity (f64 value + u32 key id); a window's log starts at
+     * 4096 entries, grows by 1.5x or to the exact need, whichever is larger,
+     * keeps its capacity when the slot is reused, and holds at most 2^31 - 1
+     * entries. A failed allocation (or that limit) is DZ_ERR with a message
+     * from the push — or from the next call into the op, for the pipelined
+     * device pushes — and loses that batch; the op stays usable for poll
+     * and destroy. */
+    DZ_AGG_MEDIAN = 16,
 } dz_agg_op;
 
 typedef enum dz_key_kind {
@@ -285,7 +308,9 @@ int64_t dz_window_op_open_windows(dz_window_op* op);
  * are already filtered). cmp: 0 '<', 1 '<=', 2 '>', 3 '>=', 4 '==', 5 '!='.
  * agg_idx indexes dz_window_desc.aggs. NULL aggregate values never pass
  * (for the variance family: the finalised value, under its own NULL rule;
- * for an aggregate on an extra value column: that column's own NULL-ness). */
+ * for an aggregate on an extra value column: that column's own NULL-ness;
+ * for the median: the finalised value, NULL for a group without a valid
+ * row). */
 dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
                                   int32_t cmp, double literal);
 
@@ -476,6 +501,12 @@ int64_t dz_debug_windows_for_range(int64_t min_ts, int64_t max_ts,
  * agg_op is not one of the four variance codes. */
 int32_t dz_debug_var_finalize(int32_t agg_op, uint64_t count, double m2,
                               double* out);
+
+/* The median kernels' edges, so tests can aim at them: *lds_vals = the
+ * largest group (in values) selected in LDS — a longer one is selected over
+ * global memory; *log_min_entries = the first allocation of a window's
+ * value log. Either pointer may be NULL. No GPU needed. */
+void dz_debug_median_caps(int32_t* lds_vals, int64_t* log_min_entries);
 
 /* Test hook for the device utf8 intern: keep only the low `bits` (1..64)
  * bits of every key fingerprint, so distinct keys collide on demand and the
