@@ -37,13 +37,17 @@ class DataStream:
         self._window = None
         self._filters = []
 
-    def window(self, group_cols, aggs, length_ms, slide_ms=None):
+    def window(self, group_cols, aggs, length_ms, slide_ms=None,
+               value_dtype=None):
         """datastream.rs:178-196 (StreamingLogicalPlanBuilder::streaming_window,
         logical_plan/mod.rs:27-60). group_cols: [key column name]; aggs:
         [(op_name, value_col_name), ...] or (op_name, value_col_name, alias).
         Up to 4 distinct value columns (the reference aggregates several
         columns in one window, examples/examples/kafka_rideshare.rs:73-75);
-        the result column is named by the alias, else by the op name."""
+        the result column is named by the alias, else by the op name.
+        value_dtype: None / "float64" (values are cast to f64, integer arrays
+        included — nothing is inferred from the arrays) or "int64" (one value
+        column, integer arrays only: min/max/sum come back as exact int64)."""
         if len(group_cols) > 1:
             raise ValueError("hot-path shape: at most one group column")
         if self._window is not None:
@@ -71,6 +75,7 @@ class DataStream:
             "value_cols": vcols,
             "length_ms": int(length_ms),
             "slide_ms": int(slide_ms) if slide_ms else 0,
+            "value_dtype": value_dtype or "float64",
         }
         return ds
 
@@ -104,7 +109,7 @@ class DataStream:
                       aggs=aggs,
                       key_kind=self._key_kind, device=self._ctx.device,
                       n_keys_hint=n_keys_hint,
-                      no_group=no_group)
+                      no_group=no_group, value_dtype=w["value_dtype"])
         for (col, cmp, lit) in self._filters:
             names = w["names"]
             if col not in names:

@@ -22,6 +22,9 @@ AGG_MEDIAN = 16
 VAR_AGGS = frozenset((AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP,
                       AGG_STDDEV_POP))
 KEY_UTF8, KEY_INT64, KEY_DENSE_INT64 = 0, 1, 2
+VALUE_F64, VALUE_INT64 = 0, 1
+VALUE_DTYPES = {"float64": VALUE_F64, "int64": VALUE_INT64}
+INT_AGGS = frozenset((AGG_MIN, AGG_MAX, AGG_SUM))  # int64 on an int64 column
 CMP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "==": 4, "!=": 5}
 AGG_BY_NAME = {"count": AGG_COUNT, "min": AGG_MIN, "max": AGG_MAX,
                "sum": AGG_SUM, "avg": AGG_AVG, "average": AGG_AVG,
@@ -120,6 +123,11 @@ def lib():
                 p, i64, ctypes.POINTER(p), ctypes.POINTER(p)]
         except AttributeError:  # older engine build (A/B hook)
             pass
+        try:
+            L.dz_window_op_set_value_type.argtypes = [p, ctypes.c_int32,
+                                                      ctypes.c_int]
+        except AttributeError:  # older engine build (A/B hook)
+            pass
         L.dz_generate_utf8.argtypes = [ctypes.c_int32, ctypes.c_uint64, i64,
                                        i64, i64, p, p, p]
         L.dz_window_op_poll.argtypes = [p, ctypes.POINTER(ctypes.POINTER(DzOutBatch))]
@@ -205,6 +213,25 @@ def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+def _value_array(vals, value_dtype):
+    """The value column as the op reads it. float64 ops cast whatever they are
+    given, as they always have. int64 ops take integers only: a float array
+    is a TypeError, never a rounding (np.int64 of 2.0**53 + 1 is already the
+    wrong number)."""
+    if value_dtype != "int64":
+        return np.ascontiguousarray(vals, np.float64)
+    a = np.asarray(vals)
+    if a.size == 0:
+        return np.zeros(0, np.int64)  # an empty list has no dtype to refuse
+    if a.dtype.kind not in "iu":
+        raise TypeError(
+            f"value_dtype='int64' op was pushed {a.dtype} values; pass an "
+            "integer array (values are never rounded on the way in)")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise TypeError("uint64 values above INT64_MAX do not fit int64")
+    return np.ascontiguousarray(a, np.int64)
+
+
 class WindowOp:
     """Python handle over dz_window_op (one partition's stream).
 
@@ -214,13 +241,23 @@ class WindowOp:
     aggregates and alias (default: the op name) names its result column; up
     to 4 distinct columns, numbered in order of first appearance. The first
     is the primary; an aggregate on any other column reports its own mask as
-    res[alias + "_valid"]."""
+    res[alias + "_valid"].
+
+    value_dtype="int64": the (single) value column is int64. push takes an
+    integer array (a float array is a TypeError), the device pushes take
+    device pointers to int64 values, and poll returns min/max/sum as
+    np.int64 arrays (sum wraps); avg and the variance family are computed on
+    (double)v. Not available with several value columns or the median."""
 
     def __init__(self, length_ms, slide_ms=0, aggs=(("count", 0), ("min", 0),
                  ("max", 0), ("avg", 0)), key_kind=KEY_UTF8, n_keys_hint=1024,
                  device=0, max_open_windows=0, ts_col=0, group_col=1,
-                 value_col=2, no_group=False):
+                 value_col=2, no_group=False, value_dtype="float64"):
+        if value_dtype not in VALUE_DTYPES:
+            raise ValueError(f"value_dtype must be one of "
+                             f"{sorted(VALUE_DTYPES)}, got {value_dtype!r}")
         self._L = lib()
+        self.value_dtype = value_dtype
         self.no_group = no_group
         if no_group:
             group_col = -1
@@ -255,6 +292,19 @@ class WindowOp:
         self._h = self._L.dz_window_op_create(ctypes.byref(d))
         if not self._h:
             raise RuntimeError(f"dz_window_op_create failed: {_err(self._L)}")
+        if value_dtype != "float64":
+            try:
+                self.set_value_type(0, VALUE_DTYPES[value_dtype])
+            except Exception:
+                self.close()
+                raise
+
+    def set_value_type(self, value_col, vtype):
+        """dz_window_op_set_value_type: legal only before the first push."""
+        self._check(self._L.dz_window_op_set_value_type(
+            self._h, value_col, vtype), "set_value_type")
+        if value_col == 0:
+            self.value_dtype = "int64" if vtype == VALUE_INT64 else "float64"
 
     def _check(self, st, what):
         if st != DZ_OK:
@@ -265,8 +315,8 @@ class WindowOp:
         list of str/bytes for utf8. val_valid_bitmap: LSB-first bitmap bytes."""
         if self._by_col:
             return self._push_by_col(ts_ms, keys, vals, val_valid_bitmap)
+        vals = _value_array(vals, self.value_dtype)
         ts_ms = np.ascontiguousarray(ts_ms, np.int64)
-        vals = np.ascontiguousarray(vals, np.float64)
         n = len(ts_ms)
         keep = []
         if self.no_group:
@@ -350,7 +400,7 @@ class WindowOp:
             cols[self._group_col] = DzColumn(
                 n, None, None, _np_ptr(karr).value if n else None)
         for c, v, bm in zip(self._dcols, vals, bitmaps):
-            v = np.ascontiguousarray(v, np.float64)
+            v = _value_array(v, self.value_dtype)
             if len(v) != n:
                 raise ValueError("value column length differs from ts")
             keep.append(v)
@@ -460,7 +510,9 @@ class WindowOp:
             res["key"] = mk(ob.key_i64, n, ctypes.c_int64)
         for i, name in enumerate(self.agg_names):
             pt = ob.agg_cols[i]
-            if self._agg_arr[i].op == AGG_COUNT:
+            if self._agg_arr[i].op == AGG_COUNT or (
+                    self.value_dtype == "int64"
+                    and self._agg_arr[i].op in INT_AGGS):
                 res[name] = mk(pt, n, ctypes.c_int64)
             else:
                 res[name] = mk(pt, n, ctypes.c_double)

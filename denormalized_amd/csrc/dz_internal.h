@@ -124,20 +124,29 @@ void launch_scatter(hipStream_t stream, const int32_t* d_kid, const int64_t* d_t
 
 constexpr int FOLD_GCAP = 256; /* groups per bucket per fold chunk */
 
+/* value type of the fold (the launches' `ival`): f64, or int64 without / with
+ * the variance family's Welford state */
+enum { FOLD_F64 = 0, FOLD_INT64 = 1, FOLD_INT64_VAR = 2 };
+
 /* fused stable-split + fold: per-(window,key) bins staged in LDS fold
  * straight into register accumulators seeded from the window-slot slabs —
  * no reordered records in HBM. v_base != null selects the variance-carrying
  * instantiation: the Welford (mean, m2) state lives in a side slab laid out
  * [slot][{mean,m2}][kcap] f64 (vslab_cells = nslots * 2 * kcap), indexed by
  * the same (slot, kloc, bucket) as the main slab and bounds-guarded through
- * d_dbg; null keeps the kernels and the traffic of ops without it. */
+ * d_dbg; null keeps the kernels and the traffic of ops without it.
+ * ival != FOLD_F64 selects the int64 instantiations: the records' 8 value
+ * bytes are an int64_t, min/max/sum are integers stored bit for bit in the
+ * s_min/s_max/s_sum cells, and the side slab (always present then) is
+ * [slot][{fsum}][kcap] (FOLD_INT64) or [slot][{fsum, mean, m2}][kcap]
+ * (FOLD_INT64_VAR), fsum = the f64 sum of (double)v in row order. */
 void launch_regroup_fold(hipStream_t stream, const uint4* d_grec,
                          const uint32_t* d_bucket_base,
                          const FoldChunk& fc, const int32_t* d_slot_of_widx,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
                          uint32_t* d_dbg, double* v_base, int64_t vslab_cells,
-                         const FoldExtras& fx);
+                         const FoldExtras& fx, int ival = FOLD_F64);
 
 void launch_regroup_l1(hipStream_t stream, const uint4* d_grec,
                        const uint32_t* d_bucket_base,
@@ -152,7 +161,8 @@ void launch_regroup_l2_fold(hipStream_t stream, const uint4* d_grec2,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
                             uint32_t* d_dbg, double* v_base,
-                            int64_t vslab_cells, const FoldExtras& fx);
+                            int64_t vslab_cells, const FoldExtras& fx,
+                            int ival = FOLD_F64);
 
 struct EGatherSlots {
     int32_t s[16];
@@ -296,6 +306,11 @@ void launch_egather_slabs(hipStream_t stream, const uint64_t* s_base,
  * the slot's m2 column from the side slab */
 void launch_egather_slabs_var(hipStream_t stream, const uint64_t* s_base,
                               const double* v_base, int64_t kcap,
+                              EGatherSlots slots, int gcount, uint64_t* out);
+/* int64-value ops: (6 or 7) * kcap cells per close — the 5-field slab, the
+ * slot's f64-sum column, then m2 when var != 0 */
+void launch_egather_slabs_int(hipStream_t stream, const uint64_t* s_base,
+                              const double* v_base, int var, int64_t kcap,
                               EGatherSlots slots, int gcount, uint64_t* out);
 /* multi-column ops: (5 + 4 nx) * kcap cells per close — the 5-field slab,
  * then the slot's extras from the side slab */

@@ -1284,7 +1284,18 @@ __device__ __forceinline__ void welford_step(double v, uint64_t n,
  * cell as the main slab, bounds-guarded through dbg[1]). The FoldExtras
  * argument exists only when NX > 0 (the trailing pack is empty otherwise), so
  * the NX=0 kernels keep their argument block and compile to the code they
- * were before extras existed. */
+ * were before extras existed.
+ * IV: the value column is int64 (dz_window_op_set_value_type). The records
+ * carry the value as 8 opaque bytes either way; here the walk reads them as
+ * int64_t and keeps min/max (signed compare) and sum (wrapping add, on
+ * uint64_t) as integers, stored bit for bit in the s_min/s_max/s_sum cells,
+ * plus one f64 running sum of (double)v in row order for avg — the
+ * reference's cast-then-average. VAR steps Welford on (double)v. The side slab
+ * of an int op is [slot][{fsum, mean, m2}][kcap] with VAR and [slot][{fsum}]
+ * [kcap] without; fsum is read only behind cnt > 0 like its neighbours, so a
+ * recycled slot's stale cell never surfaces and no reset touches it. NX == 0
+ * only. IV=false adds no variable and no statement: every branch on it is an
+ * if constexpr, and the f64 kernels compile to the code they were. */
 __device__ __forceinline__ const FoldExtras& pick_fx(const FoldExtras& f) {
     return f;
 }
@@ -1297,7 +1308,8 @@ struct XAcc {
 template <>
 struct XAcc<0> {};
 
-template <int MODE, bool VAR = false, int NX = 0, typename... XA>
+template <int MODE, bool VAR = false, int NX = 0, bool IV = false,
+          typename... XA>
 __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
         const uint32_t* bucket_base, FoldChunk fc,
         const uint32_t* b1offs, const uint32_t* b1lens, uint32_t* binoffs,
@@ -1312,6 +1324,8 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     static_assert(NX >= 0 && NX <= MAX_EXTRA_COLS &&
                   (NX == 0 || (!VAR && MODE != RG_L1)),
                   "extras ride the fold modes, without variance state");
+    static_assert(!IV || (NX == 0 && MODE != RG_L1),
+                  "int64 values ride the fold modes, single-column");
     constexpr bool FOLD = (MODE == RG_DIRECT_FOLD || MODE == RG_L2_FOLD);
     __shared__ uint32_t cnt[GCAP];    /* whole-segment bin counts (L1) */
     __shared__ uint32_t gcur[GCAP];   /* segment-region bin cursors (L1) */
@@ -1369,6 +1383,13 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     double f_mn = 0.0, f_mx = 0.0, f_sm = 0.0;
     int64_t f_vidx = 0;               /* VAR: side-slab cell of `mean` */
     double f_mean = 0.0, f_m2 = 0.0;  /* VAR: Welford state */
+    /* IV: integer min/max/sum and the f64 sum of (double)v; f_vidx is then
+     * the side-slab cell of fsum, with mean and m2 (VAR) kcap and 2 kcap
+     * cells behind it */
+    [[maybe_unused]] int64_t i_mn = 0, i_mx = 0;
+    [[maybe_unused]] uint64_t i_sm = 0;
+    [[maybe_unused]] double f_fs = 0.0;
+    constexpr int IVF = VAR ? 3 : 1; /* IV: side-slab fields per slot */
     [[maybe_unused]] int64_t f_xidx = 0; /* NX: side-slab cell of extra 0's cnt */
     [[maybe_unused]] XAcc<NX> x;         /* NX: per-extra accumulators */
     if constexpr (NX > 0) {
@@ -1398,7 +1419,15 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                 dbg[1] = 1; /* bounds guard: disown, never corrupt */
                 f_own = false;
             }
-            if (VAR) {
+            if constexpr (IV) {
+                f_vidx = slot * ((int64_t)IVF * fc.kcap) +
+                         (((int64_t)my_kloc << LOG_NB) | bkt);
+                if (slot < 0 || f_vidx < 0 ||
+                    f_vidx + (int64_t)(IVF - 1) * fc.kcap >= vslab_cells) {
+                    dbg[1] = 1;
+                    f_own = false;
+                }
+            } else if (VAR) {
                 /* same (slot, kloc, bucket) indexing, 2 fields per slot;
                  * m2 sits kcap cells after mean */
                 f_vidx = slot * (2 * fc.kcap) +
@@ -1465,7 +1494,10 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
      * register set (179 and 195 VGPRs: past the 168 that 3 waves/SIMD
      * allow): those instantiations load each supertile where it is taken
      * over */
-    constexpr bool PREFETCH = NX < 2;
+    /* so does the int64 direct fold with variance state (181 VGPRs with the
+     * second set); its two-level sibling keeps it (149) */
+    constexpr bool PREFETCH =
+        NX < 2 && !(IV && VAR && MODE == RG_DIRECT_FOLD);
     /* staged records the fold walk reads ahead of their updates; the group
      * lives in the registers recs[]/bins[] vacate after placement, and the
      * gathered extras of NX >= 2 leave room for half a group */
@@ -1566,7 +1598,18 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
                     f_loaded = true;
                     f_cnt = s_cnt[f_sidx];
                     f_fst = s_first[f_sidx];
-                    if (f_cnt > 0) {
+                    if constexpr (IV) {
+                        if (f_cnt > 0) {
+                            i_mn = (int64_t)__double_as_longlong(s_min[f_sidx]);
+                            i_mx = (int64_t)__double_as_longlong(s_max[f_sidx]);
+                            i_sm = (uint64_t)__double_as_longlong(s_sum[f_sidx]);
+                            f_fs = v_base[f_vidx];
+                            if (VAR) {
+                                f_mean = v_base[f_vidx + fc.kcap];
+                                f_m2 = v_base[f_vidx + 2 * fc.kcap];
+                            }
+                        }
+                    } else if (f_cnt > 0) {
                         f_mn = s_min[f_sidx];
                         f_mx = s_max[f_sidx];
                         f_sm = s_sum[f_sidx];
@@ -1645,12 +1688,25 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
 #pragma unroll
                     for (int i = 0; i < WALK_G; i++) {
                         const bool in = r + (uint32_t)i < seg1;
-                        const double v = __longlong_as_double(
-                            (long long)(((uint64_t)gv[i].y << 32) | gv[i].x));
+                        const uint64_t vbits =
+                            ((uint64_t)gv[i].y << 32) | gv[i].x;
+                        double v;
+                        if constexpr (IV)
+                            v = (double)(int64_t)vbits;
+                        else
+                            v = __longlong_as_double((long long)vbits);
                         const bool ok = in && (gz[i] >> 31);
-                        f_mn = (ok && (fresh || v < f_mn)) ? v : f_mn;
-                        f_mx = (ok && (fresh || v > f_mx)) ? v : f_mx;
-                        f_sm = ok ? f_sm + v : f_sm;
+                        if constexpr (IV) {
+                            const int64_t iv = (int64_t)vbits;
+                            i_mn = (ok && (fresh || iv < i_mn)) ? iv : i_mn;
+                            i_mx = (ok && (fresh || iv > i_mx)) ? iv : i_mx;
+                            i_sm = ok ? i_sm + vbits : i_sm;
+                            f_fs = ok ? f_fs + v : f_fs;
+                        } else {
+                            f_mn = (ok && (fresh || v < f_mn)) ? v : f_mn;
+                            f_mx = (ok && (fresh || v > f_mx)) ? v : f_mx;
+                            f_sm = ok ? f_sm + v : f_sm;
+                        }
                         nv += ok ? 1u : 0u;
                         fresh = fresh && !ok;
                         if (VAR) {
@@ -1693,12 +1749,23 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     if (FOLD && f_own && f_loaded) { /* untouched bins write nothing */
         s_cnt[f_sidx] = f_cnt;
         s_first[f_sidx] = f_fst;
-        s_min[f_sidx] = f_mn;
-        s_max[f_sidx] = f_mx;
-        s_sum[f_sidx] = f_sm;
-        if (VAR) {
-            v_base[f_vidx] = f_mean;
-            v_base[f_vidx + fc.kcap] = f_m2;
+        if constexpr (IV) {
+            s_min[f_sidx] = __longlong_as_double((long long)i_mn);
+            s_max[f_sidx] = __longlong_as_double((long long)i_mx);
+            s_sum[f_sidx] = __longlong_as_double((long long)i_sm);
+            v_base[f_vidx] = f_fs;
+            if (VAR) {
+                v_base[f_vidx + fc.kcap] = f_mean;
+                v_base[f_vidx + 2 * fc.kcap] = f_m2;
+            }
+        } else {
+            s_min[f_sidx] = f_mn;
+            s_max[f_sidx] = f_mx;
+            s_sum[f_sidx] = f_sm;
+            if (VAR) {
+                v_base[f_vidx] = f_mean;
+                v_base[f_vidx + fc.kcap] = f_m2;
+            }
         }
         if constexpr (NX > 0) {
             const FoldExtras& fx = pick_fx(xa...);
@@ -1717,23 +1784,30 @@ __global__ __launch_bounds__(BLOCK) void k_regroup_t(const uint4* rrec,
     }
 }
 
-/* the fold-mode launch: picks the instantiation from the variance slab and
- * the number of extra value columns (never both: create refuses that) */
+/* the fold-mode launch: picks the instantiation from the value type, the
+ * variance slab and the number of extra value columns (never two of them,
+ * except int64 with variance: create and the setter refuse the rest) */
 template <int MODE, typename... A>
 static void launch_fold_mode(dim3 grid, hipStream_t s, double* v_base,
-                             const FoldExtras& fx, A... a) {
-    if (v_base)
+                             int ival, const FoldExtras& fx, A... a) {
+    if (ival == FOLD_INT64_VAR)
+        hipLaunchKernelGGL((k_regroup_t<MODE, true, 0, true>), grid,
+                           dim3(BLOCK), 0, s, a...);
+    else if (ival == FOLD_INT64)
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 0, true>), grid,
+                           dim3(BLOCK), 0, s, a...);
+    else if (v_base)
         hipLaunchKernelGGL((k_regroup_t<MODE, true, 0>), grid, dim3(BLOCK), 0,
                            s, a...);
     else if (fx.nx == 1)
-        hipLaunchKernelGGL((k_regroup_t<MODE, false, 1, FoldExtras>), grid,
-                           dim3(BLOCK), 0, s, a..., fx);
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 1, false, FoldExtras>),
+                           grid, dim3(BLOCK), 0, s, a..., fx);
     else if (fx.nx == 2)
-        hipLaunchKernelGGL((k_regroup_t<MODE, false, 2, FoldExtras>), grid,
-                           dim3(BLOCK), 0, s, a..., fx);
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 2, false, FoldExtras>),
+                           grid, dim3(BLOCK), 0, s, a..., fx);
     else if (fx.nx == 3)
-        hipLaunchKernelGGL((k_regroup_t<MODE, false, 3, FoldExtras>), grid,
-                           dim3(BLOCK), 0, s, a..., fx);
+        hipLaunchKernelGGL((k_regroup_t<MODE, false, 3, false, FoldExtras>),
+                           grid, dim3(BLOCK), 0, s, a..., fx);
     else
         hipLaunchKernelGGL((k_regroup_t<MODE, false, 0>), grid, dim3(BLOCK), 0,
                            s, a...);
@@ -1745,9 +1819,9 @@ void launch_regroup_fold(hipStream_t s, const uint4* d_grec,
                          uint64_t* s_cnt, double* s_min, double* s_max,
                          double* s_sum, uint64_t* s_first, int64_t slab_cells,
                          uint32_t* d_dbg, double* v_base, int64_t vslab_cells,
-                         const FoldExtras& fx) {
+                         const FoldExtras& fx, int ival) {
     launch_fold_mode<RG_DIRECT_FOLD>(
-        dim3(NB), s, v_base, fx, d_grec, d_bucket_base, fc,
+        dim3(NB), s, v_base, ival, fx, d_grec, d_bucket_base, fc,
         (const uint32_t*)nullptr, (const uint32_t*)nullptr,
         (uint32_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr,
         d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first, slab_cells,
@@ -1771,10 +1845,11 @@ void launch_regroup_l2_fold(hipStream_t s, const uint4* d_grec2,
                             double* s_min, double* s_max, double* s_sum,
                             uint64_t* s_first, int64_t slab_cells,
                             uint32_t* d_dbg, double* v_base,
-                            int64_t vslab_cells, const FoldExtras& fx) {
+                            int64_t vslab_cells, const FoldExtras& fx,
+                            int ival) {
     launch_fold_mode<RG_L2_FOLD>(
-        dim3(NB, nb1), s, v_base, fx, d_grec2, d_bucket_base, fc, d_b1offs,
-        d_b1lens, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr,
+        dim3(NB, nb1), s, v_base, ival, fx, d_grec2, d_bucket_base, fc,
+        d_b1offs, d_b1lens, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr,
         d_slot_of_widx, s_cnt, s_min, s_max, s_sum, s_first, slab_cells,
         d_dbg, v_base, v_base ? vslab_cells : (int64_t)0);
 }
@@ -2230,6 +2305,39 @@ void dz::launch_egather_slabs_var(hipStream_t s, const uint64_t* s_base,
     dim3 grid(bx, gcount);
     hipLaunchKernelGGL(k_egather_slabs_var, grid, dim3(dz::BLOCK), 0, s,
                        s_base, (const uint64_t*)v_base, kcap, slots, out);
+}
+
+/* int64-value ops: each packed close is the 5-field slab, then the slot's
+ * f64-sum column and, with a variance aggregate (var != 0), its m2 column
+ * from the side slab ([slot][{fsum, mean, m2}][kcap], or [slot][{fsum}][kcap]
+ * without): 6 or 7 * kcap cells per close */
+__global__ void k_egather_slabs_int(const uint64_t* __restrict__ s_base,
+                                    const uint64_t* __restrict__ v_base,
+                                    int var, int64_t kcap,
+                                    dz::EGatherSlots slots,
+                                    uint64_t* __restrict__ out) {
+    const int g = blockIdx.y;
+    const int64_t slot = slots.s[g];
+    const int64_t ncell = (int64_t)(var ? 7 : 6) * kcap;
+    const uint64_t* src = s_base + slot * (5 * kcap);
+    const uint64_t* vs = v_base + slot * ((int64_t)(var ? 3 : 1) * kcap);
+    uint64_t* dst = out + (int64_t)g * ncell;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < ncell; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = i < 5 * kcap   ? src[i]
+                 : i < 6 * kcap ? vs[i - 5 * kcap]         /* fsum */
+                                : vs[i - 6 * kcap + 2 * kcap]; /* m2 */
+}
+
+void dz::launch_egather_slabs_int(hipStream_t s, const uint64_t* s_base,
+                                  const double* v_base, int var, int64_t kcap,
+                                  dz::EGatherSlots slots, int gcount,
+                                  uint64_t* out) {
+    int bx = (int)std::min<int64_t>(
+        ((int64_t)(var ? 7 : 6) * kcap + dz::BLOCK - 1) / dz::BLOCK, 512);
+    dim3 grid(bx, gcount);
+    hipLaunchKernelGGL(k_egather_slabs_int, grid, dim3(dz::BLOCK), 0, s,
+                       s_base, (const uint64_t*)v_base, var, kcap, slots, out);
 }
 
 /* multi-column ops: each packed close is the 5-field slab followed by the

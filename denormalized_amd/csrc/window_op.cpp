@@ -243,6 +243,22 @@ struct dz_window_op {
      * column of the packed slab; finalisation is host-side). */
     bool has_var = false;
     double* v_base = nullptr;
+    /* int64 value column (dz_window_op_set_value_type, before the first
+     * push): the value's 8 bytes are an int64_t on every push path. The fold
+     * keeps min/max/sum as integers, bit for bit in the s_min/s_max/s_sum
+     * cells, and the f64 sum of (double)v — avg's numerator — in the side
+     * slab, which such an op always has: [slot][{fsum}][kcap], or
+     * [slot][{fsum, mean, m2}][kcap] with a variance aggregate. fsum is
+     * seeded only while cnt > 0, like mean/m2, so slot reuse needs no reset.
+     * Such ops emit through the host-built path at every key count (fsum,
+     * then m2, travel as further columns of the packed slab). */
+    bool ival = false;
+    bool pushed = false; /* a push of any kind was attempted */
+    int vfields() const { return ival ? (has_var ? 3 : 1) : (has_var ? 2 : 0); }
+    int fold_ival() const {
+        return !ival ? dz::FOLD_F64
+                     : (has_var ? dz::FOLD_INT64_VAR : dz::FOLD_INT64);
+    }
     /* several value columns: the distinct input columns in order of first
      * appearance in aggs. Column 0 is the primary and rides the records and
      * the main slab exactly as on a single-column op; columns 1..nx are the
@@ -292,11 +308,13 @@ struct dz_window_op {
     int64_t med_sorted_cap = 0;
     /* 8-byte cells of one packed close in the pinned group buffers: the
      * 5-field slab, then m2 (has_var), the median (has_med) or the extras'
-     * 4 * nx fields (never together with the other two) */
+     * 4 * nx fields (never together with the other two); an int64 op's f64
+     * sum sits right behind the 5-field slab, ahead of m2 */
     int64_t close_fields() const {
-        return 5 + (has_var ? 1 : 0) + (has_med ? 1 : 0) + 4 * nx;
+        return 5 + (ival ? 1 : 0) + (has_var ? 1 : 0) + (has_med ? 1 : 0) +
+               4 * nx;
     }
-    bool host_route() const { return has_var || has_med || nx > 0; }
+    bool host_route() const { return has_var || has_med || nx > 0 || ival; }
     struct XCols { /* one push's extra columns (device pointers) */
         const double* vals[dz::MAX_EXTRA_COLS] = {};
         const uint8_t* valid[dz::MAX_EXTRA_COLS] = {};
@@ -687,14 +705,15 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
                                    span * 8, hipMemcpyDeviceToDevice, op->stream));
     }
     double* n_vbase = nullptr;
-    if (op->has_var) {
-        size_t vstride_new = (size_t)kcap_new * 2, vstride_old = (size_t)op->kcap * 2;
+    const int vf = op->vfields(); /* 2 with variance; 1 or 3 on an int64 op */
+    if (vf > 0) {
+        size_t vstride_new = (size_t)kcap_new * vf, vstride_old = (size_t)op->kcap * vf;
         CHK(op, hipMalloc(&n_vbase, vstride_new * nslots_new * 8));
         CHK(op, hipMemsetAsync(n_vbase, 0, vstride_new * nslots_new * 8, op->stream));
         for (auto& kv : op->open) {
             int32_t s = kv.second.slot;
             int64_t span = std::min(op->kcap, kcap_new);
-            for (int f = 0; f < 2; f++)
+            for (int f = 0; f < vf; f++)
                 CHK(op, hipMemcpyAsync(n_vbase + s * vstride_new + (size_t)f * kcap_new,
                                        op->v_base + s * vstride_old + (size_t)f * op->kcap,
                                        span * 8, hipMemcpyDeviceToDevice, op->stream));
@@ -721,7 +740,7 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
     for (int s = 0; s < dz_window_op::E_CSTREAMS; s++) /* emission reads s_base */
         if (op->c_streams[s])
             CHK(op, hipStreamSynchronize(op->c_streams[s]));
-    if (op->has_var) {
+    if (vf > 0) {
         hipFree(op->v_base);
         op->v_base = n_vbase;
     }
@@ -1057,8 +1076,15 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const double* f_min = (const double*)(slab + 2 * kcap);
     const double* f_max = (const double*)(slab + 3 * kcap);
     const double* f_sum = (const double*)(slab + 4 * kcap);
-    const double* f_m2 =
-        op->has_var ? (const double*)(slab + 5 * kcap) : nullptr;
+    /* int64-value ops: min/max/sum cells hold int64 bits; the f64 sum of
+     * (double)v (avg's numerator) is field 5 and pushes m2 to field 6 */
+    const bool iv = op->ival;
+    const int64_t* i_min = (const int64_t*)(slab + 2 * kcap);
+    const int64_t* i_max = (const int64_t*)(slab + 3 * kcap);
+    const int64_t* i_sum = (const int64_t*)(slab + 4 * kcap);
+    const double* f_fsum = iv ? (const double*)(slab + 5 * kcap) : nullptr;
+    const double* f_m2 = op->has_var
+        ? (const double*)(slab + (iv ? 6 : 5) * kcap) : nullptr;
     /* median-declaring ops: the close's median column is the last field */
     const double* f_med = op->has_med
         ? (const double*)(slab + (op->close_fields() - 1) * kcap) : nullptr;
@@ -1107,10 +1133,16 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const int fc = op->agg_col[op->f_idx]; /* the filtered aggregate's column */
     for (auto& p : touched) {
         int32_t k = p.second;
-        if (filter_pass(op, c_cnt[fc][k], c_min[fc][k], c_max[fc][k],
-                        c_sum[fc][k], f_m2 ? f_m2[k] : 0.0,
-                        f_med ? f_med[k] : 0.0))
-            rows.push_back(k);
+        /* an int64 min/max/sum compares as (double)value (DataFusion's
+         * Int64-vs-Float64 coercion); avg's numerator is the f64 sum */
+        const bool pass = iv
+            ? filter_pass(op, f_cnt[k], (double)i_min[k], (double)i_max[k],
+                          op->filter.field == 3 ? (double)i_sum[k] : f_fsum[k],
+                          f_m2 ? f_m2[k] : 0.0, 0.0)
+            : filter_pass(op, c_cnt[fc][k], c_min[fc][k], c_max[fc][k],
+                          c_sum[fc][k], f_m2 ? f_m2[k] : 0.0,
+                          f_med ? f_med[k] : 0.0);
+        if (pass) rows.push_back(k);
     }
     size_t n = rows.size(), na = op->aggs.size();
 
@@ -1134,7 +1166,27 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
             for (size_t i = 0; i < n; i++)
                 msk[i] = (is_count || f_cnt[rows[i]] > 0) ? 1 : 0;
         }
-        switch (op->aggs[a].op) {
+        const dz_agg_op ao = op->aggs[a].op;
+        if (iv && (ao == DZ_AGG_MIN || ao == DZ_AGG_MAX || ao == DZ_AGG_SUM)) {
+            /* int64 columns, straight from the cells' bits */
+            const int64_t* src =
+                ao == DZ_AGG_MIN ? i_min : ao == DZ_AGG_MAX ? i_max : i_sum;
+            auto& col = ob.agg_i64[a];
+            col.resize(n);
+            for (size_t i = 0; i < n; i++)
+                col[i] = f_cnt[rows[i]] ? src[rows[i]] : 0;
+            continue;
+        }
+        if (iv && ao == DZ_AGG_AVG) { /* cast-then-average */
+            auto& col = ob.agg_f64[a];
+            col.resize(n);
+            for (size_t i = 0; i < n; i++) {
+                uint64_t c = f_cnt[rows[i]];
+                col[i] = c ? f_fsum[rows[i]] / (double)c : 0.0;
+            }
+            continue;
+        }
+        switch (ao) {
             case DZ_AGG_COUNT: {
                 auto& col = ob.agg_i64[a];
                 col.resize(n);
@@ -1847,6 +1899,11 @@ static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
             if (op->has_med)
                 dz::launch_egather_slabs_med(op->copy_stream, op->s_base,
                                              op->v_base, op->d_med_out,
+                                             op->kcap, gs, gcount,
+                                             op->e_gbufs_dev[gbuf]);
+            else if (op->ival)
+                dz::launch_egather_slabs_int(op->copy_stream, op->s_base,
+                                             op->v_base, op->has_var ? 1 : 0,
                                              op->kcap, gs, gcount,
                                              op->e_gbufs_dev[gbuf]);
             else if (op->has_var)
@@ -2601,8 +2658,9 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                                            op->s_first,
                                            (int64_t)op->nslots * 5 * op->kcap,
                                            op->d_dbg, op->v_base,
-                                           (int64_t)op->nslots * 2 * op->kcap,
-                                           fx);
+                                           (int64_t)op->nslots *
+                                               op->vfields() * op->kcap,
+                                           fx, op->fold_ival());
             });
         } else {
             for (int64_t k_lo = 0; k_lo < klocs; k_lo += dz::FOLD_GCAP) {
@@ -2626,7 +2684,8 @@ static dz_status process_batch(dz_window_op* op, const dz_window_op::Pend& P) {
                             op->s_max, op->s_sum, op->s_first,
                             (int64_t)op->nslots * 5 * op->kcap, op->d_dbg,
                             op->v_base,
-                            (int64_t)op->nslots * 2 * op->kcap, fx);
+                            (int64_t)op->nslots * op->vfields() * op->kcap,
+                            fx, op->fold_ival());
                     });
                 }
             }
@@ -2708,6 +2767,61 @@ extern "C" dz_status dz_window_op_set_extra_values(
     return DZ_OK;
 }
 
+/* The value column's type. Legal only before the first push of any kind:
+ * the side slab and the pinned group buffers are re-made here for the int64
+ * layout (an f64 sum per group, a wider packed close), and nothing is open
+ * yet that would have to be carried over. Every refusal leaves the op as it
+ * was. */
+extern "C" dz_status dz_window_op_set_value_type(dz_window_op* op,
+                                                 int32_t value_col,
+                                                 dz_value_type t) {
+    if (!op) return DZ_ERR;
+    if (op->pushed) {
+        op->err = "set_value_type: legal only before the operator's first "
+                  "push";
+        return DZ_ERR;
+    }
+    if ((int32_t)t != DZ_VALUE_F64 && (int32_t)t != DZ_VALUE_INT64) {
+        op->err = "set_value_type: unknown value type " +
+                  std::to_string((int32_t)t) + " (valid: 0 f64, 1 int64)";
+        return DZ_ERR;
+    }
+    if (value_col != 0) {
+        op->err = "set_value_type: value_col " + std::to_string(value_col) +
+                  " is not supported (only the primary column, 0)";
+        return DZ_ERR;
+    }
+    if ((op->ival ? DZ_VALUE_INT64 : DZ_VALUE_F64) == (int32_t)t) return DZ_OK;
+    if (op->nx > 0) {
+        op->err = "set_value_type: int64 values need a single value column "
+                  "(several value columns are not supported with them)";
+        return DZ_ERR;
+    }
+    if (op->has_med) {
+        op->err = "set_value_type: int64 values are not supported together "
+                  "with the median aggregate";
+        return DZ_ERR;
+    }
+    CHK(op, hipSetDevice(op->device));
+    const bool want = (int32_t)t == DZ_VALUE_INT64;
+    const int vf = want ? (op->has_var ? 3 : 1) : (op->has_var ? 2 : 0);
+    double* n_vbase = nullptr;
+    if (vf > 0) {
+        const size_t bytes = (size_t)op->nslots * vf * op->kcap * 8;
+        CHK(op, hipMalloc(&n_vbase, bytes));
+        if (hipMemset(n_vbase, 0, bytes) != hipSuccess) {
+            hipFree(n_vbase);
+            op->err = "set_value_type: side slab init failed";
+            return DZ_ERR;
+        }
+    }
+    hipFree(op->v_base);
+    op->v_base = n_vbase;
+    op->ival = want;
+    op->e_slab_kcap = -1; /* the packed close changed width: re-make buffers */
+    return ensure_emission(op);
+}
+
 /* A device push's extras: the attachment set_extra_values left, consumed
  * here. Refuses (op untouched otherwise, handle usable) when a multi-column
  * op has none or its row count differs; single-column ops take nothing. */
@@ -2736,6 +2850,7 @@ extern "C" dz_status dz_window_op_push_device(dz_window_op* op, int64_t n_rows,
                                               const int32_t* d_key_ids,
                                               const double* d_vals) {
     if (!op) return DZ_ERR;
+    op->pushed = true;
     dz_window_op::XCols xc;
     if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
@@ -2775,6 +2890,7 @@ extern "C" dz_status dz_window_op_push_device_borrowed(
         dz_window_op* op, int64_t n_rows, const int64_t* d_ts_ms,
         const int32_t* d_key_ids, const double* d_vals) {
     if (!op) return DZ_ERR;
+    op->pushed = true;
     dz_window_op::XCols xc;
     if (take_extras(op, n_rows, &xc) != DZ_OK) return DZ_ERR;
     CHK(op, hipSetDevice(op->device));
@@ -2934,6 +3050,7 @@ extern "C" dz_status dz_window_op_push_device_utf8(dz_window_op* op,
         int64_t n_rows, const int64_t* d_ts_ms, const int32_t* d_key_offsets,
         const char* d_key_data, const double* d_vals) {
     if (!op) return DZ_ERR;
+    op->pushed = true;
     if (op->key_kind != DZ_KEY_UTF8 || op->no_group) {
         op->err = "push_device_utf8 requires key_kind DZ_KEY_UTF8";
         return DZ_ERR;
@@ -2984,6 +3101,7 @@ extern "C" dz_status dz_window_op_push_device_i64(dz_window_op* op,
         int64_t n_rows, const int64_t* d_ts_ms, const int64_t* d_keys,
         const double* d_vals) {
     if (!op) return DZ_ERR;
+    op->pushed = true;
     if (op->key_kind != DZ_KEY_INT64 || op->no_group) {
         op->err = "push_device_i64 requires key_kind DZ_KEY_INT64";
         return DZ_ERR;
@@ -3053,6 +3171,7 @@ extern "C" dz_status dz_generate_utf8(int32_t device, uint64_t seed,
 
 extern "C" dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch) {
     if (!op) return DZ_ERR;
+    op->pushed = true;
     if (!batch) { op->err = "null batch"; return DZ_ERR; }
     int64_t n = batch->n_rows;
     if (n == 0) return DZ_OK;
@@ -3286,7 +3405,10 @@ extern "C" dz_status dz_window_op_poll(dz_window_op* op, const dz_out_batch** ou
         ob.view.agg_valid = cols.flags;
     } else {
         for (size_t a = 0; a < op->aggs.size(); a++) {
-            if (op->aggs[a].op == DZ_AGG_COUNT)
+            const dz_agg_op ao = op->aggs[a].op;
+            if (ao == DZ_AGG_COUNT ||
+                (op->ival && (ao == DZ_AGG_MIN || ao == DZ_AGG_MAX ||
+                              ao == DZ_AGG_SUM)))
                 ob.agg_ptrs.push_back((const void*)ob.agg_i64[a].data());
             else
                 ob.agg_ptrs.push_back((const void*)ob.agg_f64[a].data());

@@ -34,6 +34,14 @@ def merge_global_partials(per_rank_batches):
                     f"merge_global_partials cannot merge {bad}: a median "
                     "does not combine from per-rank partials (it needs every "
                     "value of the window) and is not supported")
+            ints = sorted(k for k in ("min", "max", "sum") if k in b
+                          and np.asarray(b[k]).dtype.kind in "iu")
+            if ints:
+                raise ValueError(
+                    f"merge_global_partials cannot merge integer-typed "
+                    f"{ints} (an int64 value column): its float arithmetic "
+                    "would re-round them; merging int64 partials is not "
+                    "supported")
             # an aggregate on an extra value column reports its own mask as
             # "<name>_valid": such batches carry several columns' partials
             extra = sorted(k for k in b if k.endswith("_valid")

@@ -87,8 +87,15 @@ typedef enum dz_key_kind {
 
 typedef struct dz_agg_desc {
     dz_agg_op op;
-    int32_t input_col;        /* column index in the pushed batch (f64) */
+    int32_t input_col;        /* column index in the pushed batch (f64, or
+                               * int64 after dz_window_op_set_value_type) */
 } dz_agg_desc;
+
+/* The type of a value column (dz_window_op_set_value_type). */
+typedef enum dz_value_type {
+    DZ_VALUE_F64   = 0,       /* the default */
+    DZ_VALUE_INT64 = 1,
+} dz_value_type;
 
 /* Construction parameters. Mirrors what the planner hands StreamingWindowExec:
  * (mode, group-by, aggregate exprs, window type) —
@@ -159,7 +166,8 @@ typedef struct dz_out_batch {
     const int32_t* key_offsets;    /* key kind UTF8 */
     const char*    key_data;
     /* aggregate columns, one per dz_window_desc.aggs entry:
-     * COUNT -> const int64_t*, others -> const double* */
+     * COUNT -> int64; MIN/MAX/SUM of an int64 column -> int64; others ->
+     * double */
     const void* const* agg_cols;
     const uint8_t* agg_valid;      /* byte mask (1=valid) for min/max/sum/avg
                                     * (all-null groups); count is never null */
@@ -191,11 +199,46 @@ typedef struct dz_window_op dz_window_op;
  * an aggregate op code outside dz_agg_op is such an error. */
 dz_window_op* dz_window_op_create(const dz_window_desc* desc);
 
+/* Declare the type of a value column; the default is DZ_VALUE_F64.
+ * value_col is the ordinal of a distinct value column in first-appearance
+ * order; only 0 is accepted in this version. After DZ_VALUE_INT64 every push
+ * path reads the value buffer as const int64_t*: dz_window_op_push through
+ * cols[input_col].data, and the four device pushes through their d_vals
+ * argument, which keeps its const double* type — the caller casts the
+ * pointer. Validity bitmaps work as before. Per (window, key) group, over the
+ * column's valid rows (DataFusion aggregates Int64 on the column's own type:
+ * min/max/sum of Int64 yield Int64; avg and the variance family cast each
+ * value to Float64 first):
+ *   count              unchanged;
+ *   min, max           signed int64 compare; the agg_cols entry is
+ *                      const int64_t*;
+ *   sum                int64 two's-complement wrapping add (add_wrapping);
+ *                      the agg_cols entry is const int64_t*;
+ *   avg                the f64 sum of (double)v taken in row order, divided
+ *                      by (double)count — bit-exact like the f64 sum;
+ *   var_*, stddev_*    the Welford step on (double)v, with the NULL rules and
+ *                      per-aggregate masks of the f64 column.
+ * NULL-ness of min/max/sum/avg is agg_valid's, as for f64. A filter
+ * (dz_window_op_set_filter) on an int64 min/max/sum compares (double)value
+ * against the literal, which is DataFusion's Int64-vs-Float64 coercion.
+ * Int64 ops build every emitted batch on the host, at every key count.
+ * Global (no GROUP BY) ops take the same call.
+ * Legal only before the op's first push of any kind. Int64 stays single-column
+ * and without the median in this version (as the variance family stayed
+ * single-column when it arrived). DZ_ERR with one message per cause, the op
+ * left as it was and usable, for: a call after a push; an unknown type;
+ * value_col != 0; DZ_VALUE_INT64 on an op with more than one distinct value
+ * column; DZ_VALUE_INT64 on an op that declares DZ_AGG_MEDIAN. DZ_VALUE_F64
+ * on a fresh op changes nothing and returns DZ_OK. */
+dz_status dz_window_op_set_value_type(dz_window_op* op, int32_t value_col,
+                                      dz_value_type t);
+
 /* One input batch == one poll of the input stream
  * (poll_next_inner: grouped_window_agg_stream.rs:326-420): computes the batch
  * watermark, ensures window frames, routes + aggregates rows, advances the
  * shared watermark, triggers closed windows. Each aggregate reads its values
- * and its validity bitmap from batch->cols[input_col]. */
+ * and its validity bitmap from batch->cols[input_col]; the data is int64_t
+ * on an op set to DZ_VALUE_INT64. */
 dz_status dz_window_op_push(dz_window_op* op, const dz_batch* batch);
 
 /* Extra value columns (distinct input columns 1..X, in order of first
@@ -223,7 +266,8 @@ dz_status dz_window_op_set_extra_values(dz_window_op* op, int64_t n_rows,
  * any window closes complete at the NEXT call into the op (push/poll/
  * advance_watermark/finish/destroy all flush — poll opportunistically, the
  * rest unconditionally). Emitted batches and the local watermark may
- * therefore lag one device-pushed batch; results are identical. */
+ * therefore lag one device-pushed batch; results are identical.
+ * On an op set to DZ_VALUE_INT64, d_vals points at int64_t values (cast). */
 dz_status dz_window_op_push_device(dz_window_op* op, int64_t n_rows,
                                    const int64_t* d_ts_ms,
                                    const int32_t* d_key_ids,
@@ -235,7 +279,8 @@ dz_status dz_window_op_push_device(dz_window_op* op, int64_t n_rows,
  * phase consumes them). Use when the caller owns a resident stream buffer
  * (the bench; an FFI caller holding the RecordBatch across its poll-loop
  * iteration); use the staging variant above when buffer lifetime past the
- * call cannot be guaranteed. */
+ * call cannot be guaranteed.
+ * On an op set to DZ_VALUE_INT64, d_vals points at int64_t values (cast). */
 dz_status dz_window_op_push_device_borrowed(dz_window_op* op, int64_t n_rows,
                                             const int64_t* d_ts_ms,
                                             const int32_t* d_key_ids,
@@ -248,7 +293,8 @@ dz_status dz_window_op_push_device_borrowed(dz_window_op* op, int64_t n_rows,
  * offsets/data/ts/vals buffers stay valid and unmodified until the NEXT call
  * into the op. Requires key_kind DZ_KEY_UTF8. Key capacity is sized from
  * n_keys_hint at create (table 4x hint, pool 64 B/key average) and growth
- * past it fails loudly — size the hint for the stream's cardinality. */
+ * past it fails loudly — size the hint for the stream's cardinality.
+ * On an op set to DZ_VALUE_INT64, d_vals points at int64_t values (cast). */
 dz_status dz_window_op_push_device_utf8(dz_window_op* op, int64_t n_rows,
                                         const int64_t* d_ts_ms,
                                         const int32_t* d_key_offsets,
@@ -266,7 +312,8 @@ dz_status dz_window_op_push_device_utf8(dz_window_op* op, int64_t n_rows,
  * sized from n_keys_hint at create (table: the power of two >= 4x hint, at
  * least 65,536 slots; distinct keys: half the table) and growth past it
  * fails loudly — dz_window_op_finish and dz_window_op_kernel_stats return
- * DZ_ERR — so size the hint for the stream's cardinality. */
+ * DZ_ERR — so size the hint for the stream's cardinality.
+ * On an op set to DZ_VALUE_INT64, d_vals points at int64_t values (cast). */
 dz_status dz_window_op_push_device_i64(dz_window_op* op, int64_t n_rows,
                                        const int64_t* d_ts_ms,
                                        const int64_t* d_keys,
@@ -310,7 +357,8 @@ int64_t dz_window_op_open_windows(dz_window_op* op);
  * (for the variance family: the finalised value, under its own NULL rule;
  * for an aggregate on an extra value column: that column's own NULL-ness;
  * for the median: the finalised value, NULL for a group without a valid
- * row). */
+ * row; for min/max/sum of an int64 column: (double)value is compared, as
+ * DataFusion coerces Int64 against a Float64 literal). */
 dz_status dz_window_op_set_filter(dz_window_op* op, int32_t agg_idx,
                                   int32_t cmp, double literal);
 
