@@ -170,6 +170,68 @@ struct EGatherSlots {
                         * first - base, bounded by the window's row span */
 };
 
+/* Packed close (DESIGN.md §Packed close): what one closing window's state
+ * looks like in a pinned group buffer, `fields` columns of kcap 8-byte cells —
+ * the main slab's SLAB_FIELDS {cnt, first, min, max, sum}, then fsum (int64
+ * values), then m2 (variance family), then the median, or the extras'
+ * 4 * nx fields. The one place that derives it, and with it the widths of the
+ * two side slabs, from the op's kind; a field index is -1 where absent. */
+constexpr int SLAB_FIELDS = 5;
+struct CloseLayout {
+    int32_t fields = SLAB_FIELDS;   /* columns of a packed close */
+    int32_t fsum = -1, m2 = -1, med = -1, x0 = -1; /* packed column index */
+    int32_t vfields = 0;            /* v_base: [slot][vfields][kcap] */
+    int32_t v_fsum = -1, v_mean = -1, v_m2 = -1;   /* field within v_base */
+    int32_t xfields = 0;            /* x_slab: [slot][4 * nx][kcap] */
+    bool side() const { return fields > SLAB_FIELDS; }
+};
+inline CloseLayout close_layout(bool ival, bool has_var, bool has_med, int nx) {
+    CloseLayout l;
+    if (ival) { l.fsum = l.fields++; l.v_fsum = l.vfields++; }
+    if (has_var) {
+        l.m2 = l.fields++;
+        l.v_mean = l.vfields++;
+        l.v_m2 = l.vfields++;
+    }
+    if (has_med) l.med = l.fields++;
+    if (nx > 0) { l.x0 = l.fields; l.xfields = 4 * nx; l.fields += l.xfields; }
+    return l;
+}
+
+/* The gather's view of a packed close: at most 3 runs of whole columns, each
+ * read from one slab at [slot or close][stride] + off and written at column
+ * dst of the close. Travels to k_egather_close by value. */
+struct GatherSeg {
+    const uint64_t* base;
+    int64_t stride;   /* cells per slot of the source (per close: by_close) */
+    int64_t off;      /* first cell within that */
+    int64_t cells;    /* cells copied */
+    int64_t dst;      /* first cell within the packed close */
+    int32_t by_close; /* source indexed by close number, not by slot */
+};
+struct GatherDesc {
+    GatherSeg seg[3];
+    int32_t nseg = 0;
+    int64_t close_cells = 0; /* fields * kcap */
+};
+inline GatherDesc gather_desc(const CloseLayout& l, int64_t kcap,
+                              const uint64_t* s_base, const double* v_base,
+                              const uint64_t* x_slab, const double* d_med) {
+    GatherDesc d;
+    d.close_cells = l.fields * kcap;
+    auto add = [&](const void* base, int nf, int f0, int nfield, int dst,
+                   bool by_close) {
+        d.seg[d.nseg++] = {(const uint64_t*)base, nf * kcap, f0 * kcap,
+                           nfield * kcap, dst * kcap, by_close ? 1 : 0};
+    };
+    add(s_base, SLAB_FIELDS, 0, SLAB_FIELDS, 0, false);
+    if (l.fsum >= 0) add(v_base, l.vfields, l.v_fsum, 1, l.fsum, false);
+    if (l.m2 >= 0) add(v_base, l.vfields, l.v_m2, 1, l.m2, false);
+    if (l.med >= 0) add(d_med, 1, 0, 1, l.med, true);
+    if (l.x0 >= 0) add(x_slab, l.xfields, 0, l.xfields, l.x0, false);
+    return d;
+}
+
 struct EmitFilter {
     int32_t on;      /* 0 = no filter */
     int32_t field;   /* 0 cnt, 1 min, 2 max, 3 sum, 4 avg */
@@ -299,24 +361,8 @@ void launch_reset_slots_x(hipStream_t stream, const int32_t* d_slots, int ns,
 /* host-path emission: pack up to 16 closing window slots' state slabs into
  * one contiguous staging area (one launch + ONE big D2H replaces a per-close
  * copy on the push thread; slot ids travel by value in the kernel args) */
-void launch_egather_slabs(hipStream_t stream, const uint64_t* s_base,
-                          int64_t stride_u64, EGatherSlots slots, int gcount,
-                          uint64_t* out);
-/* variance-declaring ops: 6 * kcap cells per close — the 5-field slab, then
- * the slot's m2 column from the side slab */
-void launch_egather_slabs_var(hipStream_t stream, const uint64_t* s_base,
-                              const double* v_base, int64_t kcap,
-                              EGatherSlots slots, int gcount, uint64_t* out);
-/* int64-value ops: (6 or 7) * kcap cells per close — the 5-field slab, the
- * slot's f64-sum column, then m2 when var != 0 */
-void launch_egather_slabs_int(hipStream_t stream, const uint64_t* s_base,
-                              const double* v_base, int var, int64_t kcap,
-                              EGatherSlots slots, int gcount, uint64_t* out);
-/* multi-column ops: (5 + 4 nx) * kcap cells per close — the 5-field slab,
- * then the slot's extras from the side slab */
-void launch_egather_slabs_x(hipStream_t stream, const uint64_t* s_base,
-                            const uint64_t* x_slab, int nx, int64_t kcap,
-                            EGatherSlots slots, int gcount, uint64_t* out);
+void launch_egather_close(hipStream_t stream, const GatherDesc& desc,
+                          EGatherSlots slots, int gcount, uint64_t* out);
 void launch_arm_scalars(hipStream_t stream, uint64_t* scalars);
 
 /* Median (kernels.hip §MEDIAN). A window slot's value log is SoA — f64 values
@@ -356,13 +402,6 @@ void launch_med_place(hipStream_t stream, const uint32_t* d_lkid,
 void launch_med_select(hipStream_t stream, const uint64_t* d_cnt,
                        const uint32_t* d_seg_off, const double* d_sorted,
                        int64_t len, int64_t K, double* d_med, uint32_t* d_dbg);
-/* (6 or 7) * kcap cells per close: the 5-field slab, m2 when v_base != null,
- * then the close's median column d_med[close][kcap] */
-void launch_egather_slabs_med(hipStream_t stream, const uint64_t* s_base,
-                              const double* v_base, const double* d_med,
-                              int64_t kcap, EGatherSlots slots, int gcount,
-                              uint64_t* out);
-
 void launch_fill_i64(hipStream_t stream, int64_t* d_p, int64_t n, int64_t v);
 
 /* JSON ingest (kernels.hip §JSON ingest): newline count/scan, then

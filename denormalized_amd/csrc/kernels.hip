@@ -2256,116 +2256,36 @@ void launch_reset_slots_x(hipStream_t s, const int32_t* d_slots, int ns,
 
 /* ------------------------------------------------------------------ */
 /* host-path emission: pack closing slots' slabs into one staging run  */
-/* (grid.y = slot index; no per-element division)                      */
+/* (grid.y = close, grid.z = segment; no per-element division)         */
 /* ------------------------------------------------------------------ */
 
-__global__ void k_egather_slabs(const uint64_t* __restrict__ s_base,
-                                int64_t stride_u64, dz::EGatherSlots slots,
+/* One segment (blockIdx.z) of one close (blockIdx.y): a plain grid-stride copy
+ * of whole columns, from the closing slot's slab (or, by_close, the close's
+ * own row of a per-close buffer) to their place in the packed close. Blocks
+ * past a short segment's end fall through the loop. */
+__global__ void k_egather_close(dz::GatherDesc d, dz::EGatherSlots slots,
                                 uint64_t* __restrict__ out) {
     const int g = blockIdx.y;
-    const uint64_t* src = s_base + (int64_t)slots.s[g] * stride_u64;
-    uint64_t* dst = out + (int64_t)g * stride_u64;
+    const dz::GatherSeg& sg = d.seg[blockIdx.z];
+    const int64_t row = sg.by_close ? g : slots.s[g];
+    const uint64_t* __restrict__ src = sg.base + row * sg.stride + sg.off;
+    uint64_t* dst = out + (int64_t)g * d.close_cells + sg.dst;
+    const int64_t cells = sg.cells;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < stride_u64; i += (int64_t)gridDim.x * blockDim.x)
+         i < cells; i += (int64_t)gridDim.x * blockDim.x)
         dst[i] = src[i];
 }
 
-void dz::launch_egather_slabs(hipStream_t s, const uint64_t* s_base,
-                              int64_t stride_u64, dz::EGatherSlots slots,
-                              int gcount, uint64_t* out) {
-    int bx = (int)std::min<int64_t>((stride_u64 + dz::BLOCK - 1) / dz::BLOCK,
-                                    512);
-    dim3 grid(bx, gcount);
-    hipLaunchKernelGGL(k_egather_slabs, grid, dim3(dz::BLOCK), 0, s, s_base,
-                       stride_u64, slots, out);
-}
-
-/* variance-declaring ops: each packed close is the 5-field slab followed by
- * the slot's m2 column from the side slab (6 * kcap cells per close) */
-__global__ void k_egather_slabs_var(const uint64_t* __restrict__ s_base,
-                                    const uint64_t* __restrict__ v_base,
-                                    int64_t kcap, dz::EGatherSlots slots,
-                                    uint64_t* __restrict__ out) {
-    const int g = blockIdx.y;
-    const int64_t slot = slots.s[g];
-    const uint64_t* src = s_base + slot * (5 * kcap);
-    const uint64_t* m2 = v_base + slot * (2 * kcap) + kcap;
-    uint64_t* dst = out + (int64_t)g * (6 * kcap);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < 6 * kcap; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = i < 5 * kcap ? src[i] : m2[i - 5 * kcap];
-}
-
-void dz::launch_egather_slabs_var(hipStream_t s, const uint64_t* s_base,
-                                  const double* v_base, int64_t kcap,
-                                  dz::EGatherSlots slots, int gcount,
-                                  uint64_t* out) {
-    int bx = (int)std::min<int64_t>((6 * kcap + dz::BLOCK - 1) / dz::BLOCK,
-                                    512);
-    dim3 grid(bx, gcount);
-    hipLaunchKernelGGL(k_egather_slabs_var, grid, dim3(dz::BLOCK), 0, s,
-                       s_base, (const uint64_t*)v_base, kcap, slots, out);
-}
-
-/* int64-value ops: each packed close is the 5-field slab, then the slot's
- * f64-sum column and, with a variance aggregate (var != 0), its m2 column
- * from the side slab ([slot][{fsum, mean, m2}][kcap], or [slot][{fsum}][kcap]
- * without): 6 or 7 * kcap cells per close */
-__global__ void k_egather_slabs_int(const uint64_t* __restrict__ s_base,
-                                    const uint64_t* __restrict__ v_base,
-                                    int var, int64_t kcap,
-                                    dz::EGatherSlots slots,
-                                    uint64_t* __restrict__ out) {
-    const int g = blockIdx.y;
-    const int64_t slot = slots.s[g];
-    const int64_t ncell = (int64_t)(var ? 7 : 6) * kcap;
-    const uint64_t* src = s_base + slot * (5 * kcap);
-    const uint64_t* vs = v_base + slot * ((int64_t)(var ? 3 : 1) * kcap);
-    uint64_t* dst = out + (int64_t)g * ncell;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < ncell; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = i < 5 * kcap   ? src[i]
-                 : i < 6 * kcap ? vs[i - 5 * kcap]         /* fsum */
-                                : vs[i - 6 * kcap + 2 * kcap]; /* m2 */
-}
-
-void dz::launch_egather_slabs_int(hipStream_t s, const uint64_t* s_base,
-                                  const double* v_base, int var, int64_t kcap,
-                                  dz::EGatherSlots slots, int gcount,
-                                  uint64_t* out) {
-    int bx = (int)std::min<int64_t>(
-        ((int64_t)(var ? 7 : 6) * kcap + dz::BLOCK - 1) / dz::BLOCK, 512);
-    dim3 grid(bx, gcount);
-    hipLaunchKernelGGL(k_egather_slabs_int, grid, dim3(dz::BLOCK), 0, s,
-                       s_base, (const uint64_t*)v_base, var, kcap, slots, out);
-}
-
-/* multi-column ops: each packed close is the 5-field slab followed by the
- * slot's 4 * nx extra fields from the side slab ((5 + 4 nx) * kcap cells) */
-__global__ void k_egather_slabs_x(const uint64_t* __restrict__ s_base,
-                                  const uint64_t* __restrict__ x_slab, int nx,
-                                  int64_t kcap, dz::EGatherSlots slots,
-                                  uint64_t* __restrict__ out) {
-    const int g = blockIdx.y;
-    const int64_t slot = slots.s[g];
-    const int64_t ncell = (int64_t)(5 + 4 * nx) * kcap;
-    const uint64_t* src = s_base + slot * (5 * kcap);
-    const uint64_t* xs = x_slab + slot * ((int64_t)(4 * nx) * kcap);
-    uint64_t* dst = out + (int64_t)g * ncell;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < ncell; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = i < 5 * kcap ? src[i] : xs[i - 5 * kcap];
-}
-
-void dz::launch_egather_slabs_x(hipStream_t s, const uint64_t* s_base,
-                                const uint64_t* x_slab, int nx, int64_t kcap,
-                                dz::EGatherSlots slots, int gcount,
-                                uint64_t* out) {
-    int bx = (int)std::min<int64_t>(
-        ((int64_t)(5 + 4 * nx) * kcap + dz::BLOCK - 1) / dz::BLOCK, 512);
-    dim3 grid(bx, gcount);
-    hipLaunchKernelGGL(k_egather_slabs_x, grid, dim3(dz::BLOCK), 0, s, s_base,
-                       x_slab, nx, kcap, slots, out);
+void dz::launch_egather_close(hipStream_t s, const dz::GatherDesc& d,
+                              dz::EGatherSlots slots, int gcount,
+                              uint64_t* out) {
+    int64_t widest = 0;
+    for (int i = 0; i < d.nseg; i++)
+        widest = std::max(widest, d.seg[i].cells);
+    int bx = (int)std::min<int64_t>((widest + dz::BLOCK - 1) / dz::BLOCK, 512);
+    dim3 grid(bx, gcount, d.nseg);
+    hipLaunchKernelGGL(k_egather_close, grid, dim3(dz::BLOCK), 0, s, d, slots,
+                       out);
 }
 
 /* arm the per-push scalar block (min=+inf pattern, max/kid=0) in ONE tiny
@@ -3811,40 +3731,6 @@ void launch_med_select(hipStream_t s, const uint64_t* d_cnt,
     if (K <= 0) return;
     hipLaunchKernelGGL(k_med_select, dim3((uint32_t)K), dim3(BLOCK), 0, s,
                        d_cnt, d_seg_off, d_sorted, (uint32_t)len, d_med, d_dbg);
-}
-
-/* median-declaring ops: each packed close is the 5-field slab, the slot's m2
- * column when the op also declares a variance aggregate (v_base != null),
- * then the close's median column (med is [close][kcap]) */
-__global__ void k_egather_slabs_med(const uint64_t* __restrict__ s_base,
-                                    const uint64_t* __restrict__ v_base,
-                                    const uint64_t* __restrict__ med,
-                                    int64_t kcap, EGatherSlots slots,
-                                    uint64_t* __restrict__ out) {
-    const int g = blockIdx.y;
-    const int64_t slot = slots.s[g];
-    const int64_t nf = v_base ? 7 : 6;
-    const uint64_t* src = s_base + slot * (5 * kcap);
-    const uint64_t* m2 = v_base ? v_base + slot * (2 * kcap) + kcap : nullptr;
-    const uint64_t* md = med + (int64_t)g * kcap;
-    uint64_t* dst = out + (int64_t)g * (nf * kcap);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < nf * kcap; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = i < 5 * kcap ? src[i]
-               : (m2 && i < 6 * kcap) ? m2[i - 5 * kcap]
-               : md[i - (nf - 1) * kcap];
-}
-
-void launch_egather_slabs_med(hipStream_t s, const uint64_t* s_base,
-                              const double* v_base, const double* d_med,
-                              int64_t kcap, EGatherSlots slots, int gcount,
-                              uint64_t* out) {
-    const int64_t nf = v_base ? 7 : 6;
-    int bx = (int)std::min<int64_t>((nf * kcap + BLOCK - 1) / BLOCK, 512);
-    dim3 grid(bx, gcount);
-    hipLaunchKernelGGL(k_egather_slabs_med, grid, dim3(BLOCK), 0, s, s_base,
-                       (const uint64_t*)v_base, (const uint64_t*)d_med, kcap,
-                       slots, out);
 }
 
 } // namespace dz

@@ -234,27 +234,28 @@ struct dz_window_op {
     double* s_min = nullptr;
     double* s_max = nullptr;
     double* s_sum = nullptr;
-    /* variance family (has_var): Welford (mean, m2) side slab,
-     * [slot][{mean,m2}][kcap] f64 — allocated only when an aggregate of the
-     * family is declared; the main slab keeps its 5*kcap stride. Slot reuse
-     * needs no reset here: the fold seeds mean/m2 from it only while the
-     * main slab's cnt > 0, and k_reset_slots zeroes cnt. Such ops emit
-     * through the host-built path at every key count (m2 travels as a 6th
-     * column of the packed slab; finalisation is host-side). */
+    /* How this op's closes are packed and how wide its side slabs are
+     * (dz::CloseLayout): derived from has_var, ival, has_med and nx where
+     * they become final. An op with any side state emits through the
+     * host-built path at every key count. */
+    dz::CloseLayout lay;
+    int vfields() const { return lay.vfields; }
+    int64_t close_fields() const { return lay.fields; }
+    bool host_route() const { return lay.side(); }
+    /* variance family (has_var): the Welford (mean, m2) state lives in the
+     * side slab v_base, [slot][lay.vfields][kcap] f64. Slot reuse needs no
+     * reset there: the fold seeds from it only while the main slab's cnt > 0,
+     * and k_reset_slots zeroes cnt. Finalisation is host-side. */
     bool has_var = false;
     double* v_base = nullptr;
     /* int64 value column (dz_window_op_set_value_type, before the first
      * push): the value's 8 bytes are an int64_t on every push path. The fold
      * keeps min/max/sum as integers, bit for bit in the s_min/s_max/s_sum
-     * cells, and the f64 sum of (double)v — avg's numerator — in the side
-     * slab, which such an op always has: [slot][{fsum}][kcap], or
-     * [slot][{fsum, mean, m2}][kcap] with a variance aggregate. fsum is
-     * seeded only while cnt > 0, like mean/m2, so slot reuse needs no reset.
-     * Such ops emit through the host-built path at every key count (fsum,
-     * then m2, travel as further columns of the packed slab). */
+     * cells, and fsum, the f64 sum of (double)v — avg's numerator — ahead of
+     * mean and m2 in v_base, which such an op always has; fsum is seeded only
+     * while cnt > 0, like mean/m2. */
     bool ival = false;
     bool pushed = false; /* a push of any kind was attempted */
-    int vfields() const { return ival ? (has_var ? 3 : 1) : (has_var ? 2 : 0); }
     int fold_ival() const {
         return !ival ? dz::FOLD_F64
                      : (has_var ? dz::FOLD_INT64_VAR : dz::FOLD_INT64);
@@ -264,9 +265,7 @@ struct dz_window_op {
      * the main slab exactly as on a single-column op; columns 1..nx are the
      * extras, gathered by row index in the fold and kept in the side slab
      * x_slab, [slot][col][{cnt,min,max,sum}][kcap] — allocated only when
-     * nx > 0. k_reset_slots_x zeroes every extra's cnt on slot reuse. Such
-     * ops emit through the host-built path at every key count (the extras
-     * travel as 4 * nx more columns of the packed slab). */
+     * nx > 0. k_reset_slots_x zeroes every extra's cnt on slot reuse. */
     int32_t nx = 0;
     int32_t dcols[1 + dz::MAX_EXTRA_COLS] = {}; /* batch column index */
     std::vector<int32_t> agg_col;  /* per aggregate: 0 primary, 1..nx extra */
@@ -277,10 +276,9 @@ struct dz_window_op {
      * reuse. The cursor is `len`, on the host: the append reserves from
      * exact per-batch counts the host has read back, so it always knows it;
      * it returns to zero where the slot enters the reset list. At close the
-     * chain scan -> place -> select leaves med[close][kcap] in d_med_out,
-     * which travels as one more column of the packed close. Nothing below
-     * is allocated and no median kernel is launched while has_med is false.
-     * Median ops emit through the host-built path at every key count. */
+     * chain scan -> place -> select leaves med[close][kcap] in d_med_out.
+     * Nothing below is allocated and no median kernel is launched while
+     * has_med is false. */
     bool has_med = false;
     struct MedLog {
         char* base = nullptr;
@@ -306,15 +304,6 @@ struct dz_window_op {
     int64_t med_scratch_kcap = 0;
     double* d_med_sorted = nullptr;   /* the closing slot's placed values */
     int64_t med_sorted_cap = 0;
-    /* 8-byte cells of one packed close in the pinned group buffers: the
-     * 5-field slab, then m2 (has_var), the median (has_med) or the extras'
-     * 4 * nx fields (never together with the other two); an int64 op's f64
-     * sum sits right behind the 5-field slab, ahead of m2 */
-    int64_t close_fields() const {
-        return 5 + (ival ? 1 : 0) + (has_var ? 1 : 0) + (has_med ? 1 : 0) +
-               4 * nx;
-    }
-    bool host_route() const { return has_var || has_med || nx > 0 || ival; }
     struct XCols { /* one push's extra columns (device pointers) */
         const double* vals[dz::MAX_EXTRA_COLS] = {};
         const uint8_t* valid[dz::MAX_EXTRA_COLS] = {};
@@ -672,8 +661,58 @@ HostTimer::~HostTimer() {
 /* state allocation / growth                                           */
 /* ------------------------------------------------------------------ */
 
+/* One slab of `nf` 8-byte fields per slot, [slot][field][kcap], at a new
+ * capacity: allocate it, let `init` enqueue its initialisation, then enqueue
+ * the field-by-field copy of every open slot from `old` (laid out at
+ * op->kcap), all on op->stream. *out is the new slab (null for nf == 0);
+ * nothing stays allocated on failure. */
+template <typename Init>
+static dz_status slab_regrow(dz_window_op* op, const void* old, int nf,
+                             int64_t kcap_new, int32_t nslots_new, Init&& init,
+                             uint64_t** out) {
+    *out = nullptr;
+    if (nf == 0) return DZ_OK;
+    const size_t stride_new = (size_t)kcap_new * nf;
+    const size_t stride_old = (size_t)op->kcap * nf;
+    const size_t span = (size_t)std::min(op->kcap, kcap_new) * 8;
+    uint64_t* n;
+    CHK(op, hipMalloc(&n, stride_new * nslots_new * 8));
+    hipError_t e = init(n, stride_new);
+    for (auto& kv : op->open) { /* preserve open-window state */
+        const int32_t s = kv.second.slot;
+        for (int f = 0; f < nf && e == hipSuccess; f++)
+            e = hipMemcpyAsync(n + s * stride_new + (size_t)f * kcap_new,
+                               (const uint64_t*)old + s * stride_old +
+                                   (size_t)f * op->kcap,
+                               span, hipMemcpyDeviceToDevice, op->stream);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(n);
+        op->err = std::string("slab regrow: ") + hipGetErrorString(e);
+        return DZ_ERR;
+    }
+    *out = n;
+    return DZ_OK;
+}
+
+struct ZeroSlab { /* slab_regrow's init of a side slab: every cell zero */
+    dz_window_op* op;
+    int32_t nslots;
+    hipError_t operator()(uint64_t* n, size_t stride) const {
+        return hipMemsetAsync(n, 0, stride * nslots * 8, op->stream);
+    }
+};
+
+static dz_status sync_op_streams(dz_window_op* op) {
+    CHK(op, hipStreamSynchronize(op->stream));
+    for (int s = 0; s < dz_window_op::E_CSTREAMS; s++) /* emission reads s_base */
+        if (op->c_streams[s])
+            CHK(op, hipStreamSynchronize(op->c_streams[s]));
+    return DZ_OK;
+}
+
 static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_new) {
-    /* allocate fresh arrays, memset to empty, copy any open-slot regions */
+    /* fresh slabs, initialised to empty, open-slot regions copied over */
     kcap_new = std::max<int64_t>(kcap_new, dz::NB);
     kcap_new = (kcap_new + dz::NB - 1) / dz::NB * dz::NB;
     if (kcap_new / dz::NB > 65535) {
@@ -682,76 +721,50 @@ static dz_status state_alloc(dz_window_op* op, int64_t kcap_new, int32_t nslots_
     }
     if (kcap_new == op->kcap && nslots_new <= op->nslots) return DZ_OK;
     nslots_new = std::max(nslots_new, op->nslots);
-    size_t cells = (size_t)kcap_new * nslots_new * 5;
-    uint64_t* n_base;
-    CHK(op, hipMalloc(&n_base, cells * 8));
-    uint64_t* n_cnt = n_base;
-    uint64_t* n_first = n_base + kcap_new;
-    double* n_min = (double*)(n_base + 2 * kcap_new);
-    double* n_max = (double*)(n_base + 3 * kcap_new);
-    double* n_sum = (double*)(n_base + 4 * kcap_new);
-    size_t stride_new = (size_t)kcap_new * 5, stride_old = (size_t)op->kcap * 5;
-    for (int32_t s = 0; s < nslots_new; s++) {
-        CHK(op, hipMemsetAsync(n_cnt + s * stride_new, 0, kcap_new * 8, op->stream));
-        CHK(op, hipMemsetAsync(n_first + s * stride_new, 0xFF, kcap_new * 8, op->stream));
-        /* min/max/sum need no init: fold ignores them while cnt == 0 */
-    }
-    for (auto& kv : op->open) { /* preserve open-window state */
-        int32_t s = kv.second.slot;
-        int64_t span = std::min(op->kcap, kcap_new);
-        for (int f = 0; f < 5; f++)
-            CHK(op, hipMemcpyAsync(n_base + s * stride_new + (size_t)f * kcap_new,
-                                   op->s_base + s * stride_old + (size_t)f * op->kcap,
-                                   span * 8, hipMemcpyDeviceToDevice, op->stream));
-    }
-    double* n_vbase = nullptr;
-    const int vf = op->vfields(); /* 2 with variance; 1 or 3 on an int64 op */
-    if (vf > 0) {
-        size_t vstride_new = (size_t)kcap_new * vf, vstride_old = (size_t)op->kcap * vf;
-        CHK(op, hipMalloc(&n_vbase, vstride_new * nslots_new * 8));
-        CHK(op, hipMemsetAsync(n_vbase, 0, vstride_new * nslots_new * 8, op->stream));
-        for (auto& kv : op->open) {
-            int32_t s = kv.second.slot;
-            int64_t span = std::min(op->kcap, kcap_new);
-            for (int f = 0; f < vf; f++)
-                CHK(op, hipMemcpyAsync(n_vbase + s * vstride_new + (size_t)f * kcap_new,
-                                       op->v_base + s * vstride_old + (size_t)f * op->kcap,
-                                       span * 8, hipMemcpyDeviceToDevice, op->stream));
+    auto init_main = [&](uint64_t* n, size_t stride) {
+        /* cnt = 0, first = ~0; min/max/sum need no init: the fold ignores
+         * them while cnt == 0 */
+        hipError_t e = hipSuccess;
+        for (int32_t s = 0; s < nslots_new && e == hipSuccess; s++) {
+            e = hipMemsetAsync(n + s * stride, 0, kcap_new * 8, op->stream);
+            if (e == hipSuccess)
+                e = hipMemsetAsync(n + s * stride + kcap_new, 0xFF,
+                                   kcap_new * 8, op->stream);
         }
+        return e;
+    };
+    const ZeroSlab init_zero{op, nslots_new};
+    uint64_t *n_base = nullptr, *n_vbase = nullptr, *n_xslab = nullptr;
+    dz_status st = slab_regrow(op, op->s_base, dz::SLAB_FIELDS, kcap_new,
+                               nslots_new, init_main, &n_base);
+    if (st == DZ_OK)
+        st = slab_regrow(op, op->v_base, op->lay.vfields, kcap_new, nslots_new,
+                         init_zero, &n_vbase);
+    if (st == DZ_OK)
+        st = slab_regrow(op, op->x_slab, op->lay.xfields, kcap_new, nslots_new,
+                         init_zero, &n_xslab);
+    if (st == DZ_OK) st = sync_op_streams(op);
+    if (st != DZ_OK) { /* the op stays on its old slabs */
+        (void)hipFree(n_base);
+        (void)hipFree(n_vbase);
+        (void)hipFree(n_xslab);
+        return st;
     }
-    uint64_t* n_xslab = nullptr;
-    if (op->nx > 0) {
-        /* the extras' side slab regrows with the main slab: every cnt zero,
-         * open slots copied field by field */
-        const int nf = 4 * op->nx;
-        size_t xstride_new = (size_t)kcap_new * nf, xstride_old = (size_t)op->kcap * nf;
-        CHK(op, hipMalloc(&n_xslab, xstride_new * nslots_new * 8));
-        CHK(op, hipMemsetAsync(n_xslab, 0, xstride_new * nslots_new * 8, op->stream));
-        for (auto& kv : op->open) {
-            int32_t s = kv.second.slot;
-            int64_t span = std::min(op->kcap, kcap_new);
-            for (int f = 0; f < nf; f++)
-                CHK(op, hipMemcpyAsync(n_xslab + s * xstride_new + (size_t)f * kcap_new,
-                                       op->x_slab + s * xstride_old + (size_t)f * op->kcap,
-                                       span * 8, hipMemcpyDeviceToDevice, op->stream));
-        }
-    }
-    CHK(op, hipStreamSynchronize(op->stream));
-    for (int s = 0; s < dz_window_op::E_CSTREAMS; s++) /* emission reads s_base */
-        if (op->c_streams[s])
-            CHK(op, hipStreamSynchronize(op->c_streams[s]));
-    if (vf > 0) {
+    if (n_vbase) {
         hipFree(op->v_base);
-        op->v_base = n_vbase;
+        op->v_base = (double*)n_vbase;
     }
-    if (op->nx > 0) {
+    if (n_xslab) {
         hipFree(op->x_slab);
         op->x_slab = n_xslab;
     }
     hipFree(op->s_base);
     op->s_base = n_base;
-    op->s_cnt = n_cnt; op->s_first = n_first; op->s_min = n_min;
-    op->s_max = n_max; op->s_sum = n_sum;
+    op->s_cnt = n_base;
+    op->s_first = n_base + kcap_new;
+    op->s_min = (double*)(n_base + 2 * kcap_new);
+    op->s_max = (double*)(n_base + 3 * kcap_new);
+    op->s_sum = (double*)(n_base + 4 * kcap_new);
     for (int32_t s = op->nslots; s < nslots_new; s++)
         op->free_slots.push_back({s, nullptr});
     op->kcap = kcap_new;
@@ -829,6 +842,7 @@ extern "C" dz_window_op* dz_window_op_create(const dz_window_desc* desc) {
     op->has_var = any_var;
     op->has_med = any_med;
     op->nx = ndc - 1;
+    op->lay = dz::close_layout(op->ival, op->has_var, op->has_med, op->nx);
     memcpy(op->dcols, dcols, sizeof(dcols[0]) * ndc);
     op->agg_col = agg_col;
     op->device = desc->device;
@@ -1063,9 +1077,24 @@ static void build_keys(dz_window_op* op, const Id* ids, size_t n, OutBuf& ob,
     }
 }
 
-/* Build one emitted batch from a pinned copy of a slot slab
- * ([cnt][first][min][max][sum], each `kcap` 8-byte entries; variance-
- * declaring ops append [m2] from the side slab). Runs on the
+/* An int64-value op serves min, max and sum as int64 columns, straight from
+ * the cells' bits (count is an int64 column on every op). */
+static bool int64_value_agg(const dz_window_op* op, dz_agg_op ao) {
+    return op->ival &&
+           (ao == DZ_AGG_MIN || ao == DZ_AGG_MAX || ao == DZ_AGG_SUM);
+}
+
+/* col[i] = the group's accumulator, or 0 while the column has no valid row */
+template <typename T>
+static void put_or_zero(std::vector<T>& col, const std::vector<int32_t>& rows,
+                        const uint64_t* cnt, const T* src) {
+    col.resize(rows.size());
+    for (size_t i = 0; i < rows.size(); i++)
+        col[i] = cnt[rows[i]] ? src[rows[i]] : T(0);
+}
+
+/* Build one emitted batch from a packed close (dz::CloseLayout: `kcap`
+ * 8-byte entries per field, [cnt][first][min][max][sum] first). Runs on the
  * emission worker thread: touches only immutable config, the ChunkedDict
  * dictionaries (indices < the job's n_keys snapshot) and the slab. */
 static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
@@ -1076,26 +1105,27 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
     const double* f_min = (const double*)(slab + 2 * kcap);
     const double* f_max = (const double*)(slab + 3 * kcap);
     const double* f_sum = (const double*)(slab + 4 * kcap);
-    /* int64-value ops: min/max/sum cells hold int64 bits; the f64 sum of
-     * (double)v (avg's numerator) is field 5 and pushes m2 to field 6 */
+    /* int64-value ops: min/max/sum cells hold int64 bits, and avg's
+     * numerator is the f64 sum of (double)v */
+    const dz::CloseLayout& L = op->lay;
+    auto field = [&](int f) {
+        return f < 0 ? nullptr : (const double*)(slab + (int64_t)f * kcap);
+    };
     const bool iv = op->ival;
-    const int64_t* i_min = (const int64_t*)(slab + 2 * kcap);
-    const int64_t* i_max = (const int64_t*)(slab + 3 * kcap);
-    const int64_t* i_sum = (const int64_t*)(slab + 4 * kcap);
-    const double* f_fsum = iv ? (const double*)(slab + 5 * kcap) : nullptr;
-    const double* f_m2 = op->has_var
-        ? (const double*)(slab + (iv ? 6 : 5) * kcap) : nullptr;
-    /* median-declaring ops: the close's median column is the last field */
-    const double* f_med = op->has_med
-        ? (const double*)(slab + (op->close_fields() - 1) * kcap) : nullptr;
+    const int64_t* i_min = (const int64_t*)f_min;
+    const int64_t* i_max = (const int64_t*)f_max;
+    const int64_t* i_sum = (const int64_t*)f_sum;
+    const double* f_fsum = field(L.fsum);
+    const double* f_m2 = field(L.m2);
+    const double* f_med = field(L.med);
     /* multi-column ops: column c's (cnt, min, max, sum) — the main slab's for
-     * the primary, fields 5 + 4 (c - 1) .. of the packed close for extra c */
+     * the primary, four fields from L.x0 + 4 (c - 1) for extra c */
     const uint64_t* c_cnt[1 + dz::MAX_EXTRA_COLS] = {f_cnt};
     const double* c_min[1 + dz::MAX_EXTRA_COLS] = {f_min};
     const double* c_max[1 + dz::MAX_EXTRA_COLS] = {f_max};
     const double* c_sum[1 + dz::MAX_EXTRA_COLS] = {f_sum};
     for (int c = 1; c <= op->nx; c++) {
-        const uint64_t* x = slab + (int64_t)(5 + 4 * (c - 1)) * kcap;
+        const uint64_t* x = slab + (int64_t)(L.x0 + 4 * (c - 1)) * kcap;
         c_cnt[c] = x;
         c_min[c] = (const double*)(x + kcap);
         c_max[c] = (const double*)(x + 2 * kcap);
@@ -1167,23 +1197,10 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                 msk[i] = (is_count || f_cnt[rows[i]] > 0) ? 1 : 0;
         }
         const dz_agg_op ao = op->aggs[a].op;
-        if (iv && (ao == DZ_AGG_MIN || ao == DZ_AGG_MAX || ao == DZ_AGG_SUM)) {
-            /* int64 columns, straight from the cells' bits */
-            const int64_t* src =
-                ao == DZ_AGG_MIN ? i_min : ao == DZ_AGG_MAX ? i_max : i_sum;
-            auto& col = ob.agg_i64[a];
-            col.resize(n);
-            for (size_t i = 0; i < n; i++)
-                col[i] = f_cnt[rows[i]] ? src[rows[i]] : 0;
-            continue;
-        }
-        if (iv && ao == DZ_AGG_AVG) { /* cast-then-average */
-            auto& col = ob.agg_f64[a];
-            col.resize(n);
-            for (size_t i = 0; i < n; i++) {
-                uint64_t c = f_cnt[rows[i]];
-                col[i] = c ? f_fsum[rows[i]] / (double)c : 0.0;
-            }
+        if (int64_value_agg(op, ao)) {
+            put_or_zero(ob.agg_i64[a], rows, f_cnt,
+                        ao == DZ_AGG_MIN ? i_min
+                                         : ao == DZ_AGG_MAX ? i_max : i_sum);
             continue;
         }
         switch (ao) {
@@ -1193,33 +1210,18 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                 for (size_t i = 0; i < n; i++) col[i] = (int64_t)f_cnt[rows[i]];
                 break;
             }
-            case DZ_AGG_MIN: {
-                auto& col = ob.agg_f64[a];
-                col.resize(n);
-                for (size_t i = 0; i < n; i++)
-                    col[i] = f_cnt[rows[i]] ? f_min[rows[i]] : 0.0;
-                break;
-            }
-            case DZ_AGG_MAX: {
-                auto& col = ob.agg_f64[a];
-                col.resize(n);
-                for (size_t i = 0; i < n; i++)
-                    col[i] = f_cnt[rows[i]] ? f_max[rows[i]] : 0.0;
-                break;
-            }
-            case DZ_AGG_SUM: {
-                auto& col = ob.agg_f64[a];
-                col.resize(n);
-                for (size_t i = 0; i < n; i++)
-                    col[i] = f_cnt[rows[i]] ? f_sum[rows[i]] : 0.0;
-                break;
-            }
+            case DZ_AGG_MIN: put_or_zero(ob.agg_f64[a], rows, f_cnt, f_min); break;
+            case DZ_AGG_MAX: put_or_zero(ob.agg_f64[a], rows, f_cnt, f_max); break;
+            case DZ_AGG_SUM: put_or_zero(ob.agg_f64[a], rows, f_cnt, f_sum); break;
+            case DZ_AGG_MEDIAN: put_or_zero(ob.agg_f64[a], rows, f_cnt, f_med); break;
             case DZ_AGG_AVG: {
+                /* an int64 op casts, then averages: its numerator is fsum */
+                const double* num = iv ? f_fsum : f_sum;
                 auto& col = ob.agg_f64[a];
                 col.resize(n);
                 for (size_t i = 0; i < n; i++) {
                     uint64_t c = f_cnt[rows[i]];
-                    col[i] = c ? f_sum[rows[i]] / (double)c : 0.0;
+                    col[i] = c ? num[rows[i]] / (double)c : 0.0;
                 }
                 break;
             }
@@ -1235,13 +1237,6 @@ static void build_emission_host(dz_window_op* op, int64_t wstart, int64_t wend,
                     msk[i] = (uint8_t)dz_debug_var_finalize(
                         op->aggs[a].op, f_cnt[rows[i]], f_m2[rows[i]],
                         &col[i]);
-                break;
-            }
-            case DZ_AGG_MEDIAN: {
-                auto& col = ob.agg_f64[a];
-                col.resize(n);
-                for (size_t i = 0; i < n; i++)
-                    col[i] = f_cnt[rows[i]] ? f_med[rows[i]] : 0.0;
                 break;
             }
         }
@@ -1599,10 +1594,10 @@ static dz_status ensure_emission(dz_window_op* op) {
                 hipHostFree(op->e_gbufs[i]);
                 op->e_gbufs[i] = nullptr;
             }
-        /* variance-declaring and multi-column ops emit host-built at EVERY
-         * key count, so their group buffers exist at every kcap: as many
-         * whole packed closes (6, or 5 + 4 nx, columns) as fit a 64 MiB
-         * budget (at least one, at most EGROUP) */
+        /* ops with side state emit host-built at EVERY key count, so their
+         * group buffers exist at every kcap: as many whole packed closes
+         * (lay.fields columns) as fit a 64 MiB budget (at least one, at most
+         * EGROUP) */
         bool have_gbufs = kc <= 65536 || op->host_route();
         op->e_gbuf_closes = dz_window_op::E_POOL / 2;
         if (op->host_route())
@@ -1887,38 +1882,18 @@ static dz_status enqueue_group_host(dz_window_op* op, const Closed* cl,
          * fully asynchronous for the push thread (hipMemcpyAsync D2H
          * was measured performing the transfer at ENQUEUE time) */
         HostTimer htg(op, "h_trig_gather");
-        if (op->host_route()) {
-            if ((int64_t)gcount * op->close_fields() * op->kcap >
-                op->e_gbuf_cells) {
-                op->err = "internal: emission group of " +
-                          std::to_string(gcount) + " closes x " +
-                          std::to_string(op->kcap) +
-                          " keys overflows the pinned group buffer";
-                return DZ_ERR;
-            }
-            if (op->has_med)
-                dz::launch_egather_slabs_med(op->copy_stream, op->s_base,
-                                             op->v_base, op->d_med_out,
-                                             op->kcap, gs, gcount,
-                                             op->e_gbufs_dev[gbuf]);
-            else if (op->ival)
-                dz::launch_egather_slabs_int(op->copy_stream, op->s_base,
-                                             op->v_base, op->has_var ? 1 : 0,
-                                             op->kcap, gs, gcount,
-                                             op->e_gbufs_dev[gbuf]);
-            else if (op->has_var)
-                dz::launch_egather_slabs_var(op->copy_stream, op->s_base,
-                                             op->v_base, op->kcap, gs, gcount,
-                                             op->e_gbufs_dev[gbuf]);
-            else
-                dz::launch_egather_slabs_x(op->copy_stream, op->s_base,
-                                           op->x_slab, op->nx, op->kcap, gs,
-                                           gcount, op->e_gbufs_dev[gbuf]);
-        } else {
-            dz::launch_egather_slabs(op->copy_stream, op->s_base,
-                                     op->kcap * 5, gs, gcount,
-                                     op->e_gbufs_dev[gbuf]);
+        const dz::GatherDesc gd =
+            dz::gather_desc(op->lay, op->kcap, op->s_base, op->v_base,
+                            op->x_slab, op->d_med_out);
+        if (gcount * gd.close_cells > op->e_gbuf_cells) {
+            op->err = "internal: emission group of " +
+                      std::to_string(gcount) + " closes x " +
+                      std::to_string(op->kcap) +
+                      " keys overflows the pinned group buffer";
+            return DZ_ERR;
         }
+        dz::launch_egather_close(op->copy_stream, gd, gs, gcount,
+                                 op->e_gbufs_dev[gbuf]);
         CHK(op, hipEventRecord(fr, op->copy_stream));
         CHK(op, hipEventRecord(gev, op->copy_stream));
     }
@@ -2804,20 +2779,17 @@ extern "C" dz_status dz_window_op_set_value_type(dz_window_op* op,
     }
     CHK(op, hipSetDevice(op->device));
     const bool want = (int32_t)t == DZ_VALUE_INT64;
-    const int vf = want ? (op->has_var ? 3 : 1) : (op->has_var ? 2 : 0);
-    double* n_vbase = nullptr;
-    if (vf > 0) {
-        const size_t bytes = (size_t)op->nslots * vf * op->kcap * 8;
-        CHK(op, hipMalloc(&n_vbase, bytes));
-        if (hipMemset(n_vbase, 0, bytes) != hipSuccess) {
-            hipFree(n_vbase);
-            op->err = "set_value_type: side slab init failed";
-            return DZ_ERR;
-        }
-    }
+    const dz::CloseLayout lay =
+        dz::close_layout(want, op->has_var, op->has_med, op->nx);
+    uint64_t* n_vbase = nullptr;
+    /* nothing is open: allocate plus zero */
+    if (slab_regrow(op, nullptr, lay.vfields, op->kcap, op->nslots,
+                    ZeroSlab{op, op->nslots}, &n_vbase) != DZ_OK)
+        return DZ_ERR;
     hipFree(op->v_base);
-    op->v_base = n_vbase;
+    op->v_base = (double*)n_vbase;
     op->ival = want;
+    op->lay = lay;
     op->e_slab_kcap = -1; /* the packed close changed width: re-make buffers */
     return ensure_emission(op);
 }
@@ -3406,9 +3378,7 @@ extern "C" dz_status dz_window_op_poll(dz_window_op* op, const dz_out_batch** ou
     } else {
         for (size_t a = 0; a < op->aggs.size(); a++) {
             const dz_agg_op ao = op->aggs[a].op;
-            if (ao == DZ_AGG_COUNT ||
-                (op->ival && (ao == DZ_AGG_MIN || ao == DZ_AGG_MAX ||
-                              ao == DZ_AGG_SUM)))
+            if (ao == DZ_AGG_COUNT || int64_value_agg(op, ao))
                 ob.agg_ptrs.push_back((const void*)ob.agg_i64[a].data());
             else
                 ob.agg_ptrs.push_back((const void*)ob.agg_f64[a].data());

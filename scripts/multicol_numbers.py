@@ -18,7 +18,8 @@ are the same generator under other seeds.
 
 fold_ms_per_launch is the `regfold` row of kernel_stats() (HIP events on
 every 8th launch, scaled to all launches) divided by its launches, summed
-over the ops of a split run.
+over the ops of a split run. gather_ms_per_step is the `h_trig_gather` row the
+same way: push-thread wall time spent enqueueing the close gather, per step.
 """
 import argparse
 import ctypes
@@ -94,13 +95,16 @@ def main():
                 n += b["n_rows"]
         return n
 
-    def fold():  # (summed scaled ms, launches) over the ops
+    def stat(name):  # (summed scaled ms, launches) over the ops
         ms = ln = 0
         for op in ops:
-            st = op.kernel_stats()["regfold"]
+            st = op.kernel_stats().get(name, {"total_ms": 0, "launches": 0})
             ms += st["total_ms"]
             ln += st["launches"]
         return ms, ln
+
+    def fold():
+        return stat("regfold")
 
     out_rows = 0
     for s in range(a.warmup):
@@ -110,7 +114,7 @@ def main():
         op.drain()
     consume()
     dz.synchronize(dev)
-    f0 = fold()
+    f0, g0 = fold(), stat("h_trig_gather")
     t0 = time.perf_counter()
     for s in range(a.warmup, total):
         push(s)
@@ -120,7 +124,7 @@ def main():
     out_rows += consume()
     dz.synchronize(dev)
     dt = time.perf_counter() - t0
-    f1 = fold()
+    f1, g1 = fold(), stat("h_trig_gather")
     res = {"mode": a.mode, "cols": K, "keys": a.keys, "rows": B,
            "steps": a.steps,
            "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -128,6 +132,8 @@ def main():
            # per op-launch; a split step runs K of them
            "fold_ms_per_launch": round((f1[0] - f0[0]) / max(1, f1[1] - f0[1]), 4),
            "fold_launches_per_step": round((f1[1] - f0[1]) / a.steps, 2),
+           "gather_ms_per_step": round((g1[0] - g0[0]) / a.steps, 4),
+           "gather_launches": g1[1] - g0[1],
            "emitted_rows": out_rows}
     for op in ops:
         op.finish()
