@@ -66,6 +66,7 @@ def expected(exp, batches, valids=None):
     seen = set()
     for r in range(n):
         g = (int(exp["window_start"][r]), int(exp["key"][r]))
+        # late data re-creating a closed window: tests/streamref.py covers it
         assert g not in seen, "group emitted twice: late data is out of scope"
         seen.add(g)
         v, m, count = state.get(g, (0.0, 0, 0))

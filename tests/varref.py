@@ -93,6 +93,7 @@ def expected(exp, batches, valids=None):
     seen = set()
     for r in range(n):
         g = (int(exp["window_start"][r]), int(exp["key"][r]))
+        # disordered or late streams: tests/streamref.py is the reference
         assert g not in seen, "group emitted twice: late data is out of scope"
         seen.add(g)
         count, m2 = state.get(g, (0, 0.0))
