@@ -33,15 +33,17 @@ def median(values):
         return float((s[n // 2 - 1] + s[n // 2]) / np.float64(2.0)), 1
 
 
-def expected(exp, batches, valids=None):
+def expected(exp, batches, valids=None, slide_ms=None):
     """Median column for the oracle's emitted rows.
 
     exp: Oracle.fetch() dict for the same `batches` [(ts, key, val), ...].
     A window's rows are selected by membership, start <= ts < end, per emitted
     window, so timestamps need no order; every (window, key) must be emitted
     once (no late data reopening a closed window). valids: per-batch 0/1
-    arrays or None. Returns (values f64[n], valid u8[n]) row-aligned with
-    exp."""
+    arrays or None. slide_ms: the sliding hop; needed when it does not divide
+    the snap unit (varref.in_own_grid), harmless otherwise. Returns (values
+    f64[n], valid u8[n]) row-aligned with exp."""
+    from tests.varref import in_own_grid
     ts = np.concatenate([np.asarray(b[0], np.int64) for b in batches])
     keys = np.concatenate([np.asarray(b[1], np.int64) for b in batches])
     vals = np.concatenate([np.asarray(b[2], np.float64) for b in batches])
@@ -57,7 +59,10 @@ def expected(exp, batches, valids=None):
     wins = sorted(set(zip(exp["window_start"].tolist(),
                           exp["window_end"].tolist())))
     for ws, we in wins:
-        sel = np.flatnonzero((ts >= ws) & (ts < we) & ok)
+        own = (ts >= ws) & (ts < we) & ok
+        if slide_ms:
+            own &= in_own_grid(batches, ws, we - ws, slide_ms)
+        sel = np.flatnonzero(own)
         order = sel[np.argsort(keys[sel], kind="stable")]
         cuts = np.flatnonzero(np.diff(keys[order])) + 1
         for seg in np.split(order, cuts):

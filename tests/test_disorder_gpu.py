@@ -69,9 +69,11 @@ def _fields(names, no_group=False):
 
 
 def run_gpu(fam, len_ms, slide_ms, batches, valids=None, filt=None,
-            dense=False, no_group=False, n_keys_hint=64, stats=None, **kw):
+            dense=False, no_group=False, n_keys_hint=64, stats=None,
+            on_push=None, **kw):
     """Host-push `batches` [(ts, keys, values), ...] through one op of the
-    family; the emitted rows concatenated per column, in emitted order."""
+    family; the emitted rows concatenated per column, in emitted order.
+    on_push(batch index, op) runs after every push."""
     from denormalized_amd import WindowOp, _lib
     names, dtype = FAMILIES[fam]
     op = WindowOp(length_ms=len_ms, slide_ms=slide_ms,
@@ -85,6 +87,8 @@ def run_gpu(fam, len_ms, slide_ms, batches, valids=None, filt=None,
     for bi, (ts, k, v) in enumerate(batches):
         op.push(ts, None if no_group else k, v,
                 _bitmap(None if valids is None else valids[bi]))
+        if on_push is not None:
+            on_push(bi, op)
         outs += op.poll_all()
     op.finish()
     outs += op.poll_all()

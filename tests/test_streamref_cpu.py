@@ -12,7 +12,11 @@ from tests import intref, medianref, multicolref, streamref, varref
 
 T0 = 1_000_000
 SPECIALS = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0])
-SHAPES = [(1000, 0), (2000, 500), (250, 0), (500, 100)]
+# the last four: slide does not divide the snap unit (whole seconds for
+# len >= 1000, multiples of len below), so every batch anchors its sliding
+# grid at another phase and starts of several residues mod slide interleave
+DRIFT = [(1000, 300), (700, 300), (1500, 400), (250, 100)]
+SHAPES = [(1000, 0), (2000, 500), (250, 0), (500, 100)] + DRIFT
 
 
 def fuzz_stream(seed, len_ms, mode, nb=6, n=500, nkeys=9, ints=False):
@@ -114,9 +118,42 @@ def test_signed_zero_and_leading_nan_pins():
     assert not np.signbit(got["sum"][3])
 
 
+# ------------------------------------------------- the sliding grid's phase
+
+def test_sliding_grid_phase_drifts_between_batches():
+    """A batch's sliding grid is anchored at snap(min_ts - len). For
+    (1000, 300) the snap is to whole seconds, which 300 does not divide: two
+    batches whose minima lie in different seconds get starts of different
+    residues mod 300, and the engine's host window list says the same."""
+    import ctypes
+
+    import __graft_entry__ as graft
+    from tests.pyref import windows_for_range
+    graft.build()
+    from denormalized_amd import _lib
+    L = _lib.lib()
+    ws, we = np.empty(64, np.int64), np.empty(64, np.int64)
+    residues = []
+    for mn in (T0 + 137, T0 + 1237):
+        mx = mn + 1399
+        exp = windows_for_range(mn, mx, 1000, 300)
+        n = L.dz_debug_windows_for_range(
+            mn, mx, 1000, 300, ws.ctypes.data_as(ctypes.c_void_p),
+            we.ctypes.data_as(ctypes.c_void_p), 64)
+        assert n == len(exp) > 0
+        assert ws[:n].tolist() == [s for s, _e in exp]
+        assert we[:n].tolist() == [e for _s, e in exp]
+        anchor = (mn - 1000) // 1000 * 1000
+        assert all((s - anchor) % 300 == 0 for s, _e in exp)
+        res = {s % 300 for s, _e in exp}
+        assert len(res) == 1
+        residues.append(res.pop())
+    assert residues[0] != residues[1]
+
+
 # ------------------------------------------- against varref and medianref
 
-@pytest.mark.parametrize("len_ms,slide_ms", [(1000, 0), (500, 100)])
+@pytest.mark.parametrize("len_ms,slide_ms", [(1000, 0), (500, 100)] + DRIFT)
 def test_matches_varref_and_medianref_on_sorted_streams(len_ms, slide_ms):
     rng = np.random.default_rng(41 + len_ms)
     n = 4500
@@ -135,14 +172,14 @@ def test_matches_varref_and_medianref_on_sorted_streams(len_ms, slide_ms):
     got = streamref.run(len_ms, slide_ms, batches, valids).fetch()
     assert np.array_equal(got["key"], exp["key"])
     assert np.array_equal(got["window_start"], exp["window_start"])
-    var = varref.expected(exp, batches, valids)
+    var = varref.expected(exp, batches, valids, slide_ms)
     for name in varref.OPS:
         vals_, msk = var[name]
         assert np.array_equal(got[name + "_valid"], msk), name
         assert 0 < msk.sum() < len(msk), name
         assert np.array_equal(got[name].view(np.uint64),
                               vals_.view(np.uint64)), name
-    mvals, mmask = medianref.expected(exp, batches, valids)
+    mvals, mmask = medianref.expected(exp, batches, valids, slide_ms)
     assert np.array_equal(got["valid"], mmask)
     assert np.array_equal(got["median"].view(np.uint64),
                           mvals.view(np.uint64))
@@ -166,7 +203,7 @@ def test_median_of_specials_matches_medianref():
 # ----------------------------------------------------------- against intref
 
 @pytest.mark.parametrize("mode", ["late", "shuffled"])
-@pytest.mark.parametrize("len_ms,slide_ms", [(1000, 0), (500, 100)])
+@pytest.mark.parametrize("len_ms,slide_ms", [(1000, 0), (500, 100)] + DRIFT)
 @pytest.mark.parametrize("no_group", [False, True])
 def test_matches_intref_on_int64_streams(len_ms, slide_ms, mode, no_group):
     batches, valids = fuzz_stream(77 + len_ms, len_ms, mode, ints=True)

@@ -56,13 +56,27 @@ def finalize(op, count, m2):
     return v, 1
 
 
-def expected(exp, batches, valids=None):
+def in_own_grid(batches, ws, len_ms, slide_ms):
+    """Per row of the concatenated batches: does its own batch's window list
+    hold the start `ws`? A sliding grid is anchored per batch, so when the
+    slide does not divide the snap unit a frame receives rows only from the
+    batches whose list contains its start."""
+    from tests.pyref import windows_for_range
+    has = [any(s == ws for s, _e in windows_for_range(
+               int(np.min(b[0])), int(np.max(b[0])), len_ms, slide_ms))
+           for b in batches]
+    return np.repeat(np.array(has, bool), [len(b[0]) for b in batches])
+
+
+def expected(exp, batches, valids=None, slide_ms=None):
     """Welford columns for the oracle's emitted rows.
 
     exp: Oracle.fetch() dict for the same `batches` [(ts, key, val), ...],
     whose timestamps are non-decreasing across the whole stream, so every
     (window, key) is emitted once and a window's rows are one contiguous
     run [start <= ts < end). valids: per-batch 0/1 arrays or None.
+    slide_ms: the sliding hop; needed when it does not divide the snap unit
+    (in_own_grid), harmless otherwise.
     Returns {name: (values f64[n], valid u8[n])} for the four canonical
     names, row-aligned with exp."""
     ts = np.concatenate([np.asarray(b[0], np.int64) for b in batches])
@@ -82,7 +96,10 @@ def expected(exp, batches, valids=None):
                           exp["window_end"].tolist())))
     for ws, we in wins:
         lo, hi = np.searchsorted(ts, [ws, we], side="left")
-        sel = np.flatnonzero(ok[lo:hi]) + lo
+        own = ok[lo:hi]
+        if slide_ms:
+            own = own & in_own_grid(batches, ws, we - ws, slide_ms)[lo:hi]
+        sel = np.flatnonzero(own) + lo
         order = sel[np.argsort(keys[sel], kind="stable")]  # row order per key
         ks = keys[order]
         cuts = np.flatnonzero(np.diff(ks)) + 1
