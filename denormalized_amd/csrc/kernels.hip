@@ -10,11 +10,10 @@
  *   k_hist     per-chunk bucket histogram (bucket = key_id & (NB-1)),
  *              with per-row window multiplicity (sliding windows expand)
  *   k_scan_*   bucket bases + per-chunk stable offsets
- *   k_scatter  stable partition: records (meta,rowidx,value) land in bucket
- *              regions IN GLOBAL ROW ORDER (weighted intra-wave ranks via
- *              wave-64 shuffles + wave-serialized LDS cursors);
- *              k_scatter_tumbling is the same partition for plain tumbling
- *              batches, each row read once and held in registers
+ *   k_scatter_t<MULT>  stable partition: records (meta,rowidx,value) land in
+ *              bucket regions IN GLOBAL ROW ORDER, each row read once and
+ *              held in registers (MULT: sliding rows expand to one record
+ *              per window, weighted intra-wave ranks via readlane)
  *   k_regroup_t<RG_*_FOLD>  one block per bucket (or (bucket,bin1) segment):
  *              stable per-supertile split of the bucket's records into
  *              per-(window,key) bins IN LDS, then each bin's staged segment
@@ -31,6 +30,7 @@
 #include "dz_internal.h"
 
 #include <algorithm>
+#include <cassert>
 
 namespace dz {
 
@@ -822,189 +822,6 @@ void launch_scan(hipStream_t s, const uint32_t* d_ghist, int C,
 /* stable scatter                                                      */
 /* ------------------------------------------------------------------ */
 
-__global__ __launch_bounds__(BLOCK) void k_scatter(const int32_t* kid,
-        const int64_t* ts, const double* vals, const uint8_t* validity,
-        int64_t n, int64_t chunk, int32_t st_rows, WinParams wp,
-        const uint32_t* gofs, uint4* grec, uint32_t rec_limit,
-        uint32_t* dbg) {
-    /* LDS-staged stable partition. Each wave owns a CONTIGUOUS QUARTER of the
-     * supertile (wave order == row order), so staging cursors are per-wave
-     * private: no cross-wave serialization. A supertile costs 23 block
-     * barriers here, 17 of them in the Hillis-Steele prefix; this kernel now
-     * serves only the sliding and subrange-split launches (the plain
-     * tumbling batch runs k_scatter_tumbling below: 4 barriers, one read).
-     * Records are placed bucket-major in LDS and flushed so adjacent lanes
-     * write adjacent global addresses (the direct form measured 6x write
-     * amplification — profiles/hbm_traffic.json). A sector-aligned carrying
-     * variant (hold back <=3 records per bucket to end runs on 64 B
-     * boundaries) was measured in round 2 and REMOVED: whole-pipeline HBM
-     * traffic is ~1 TB/s against the ~6.3 TB/s achievable — the pipeline is
-     * latency-bound, and the carrying's extra flush work cost more kernel
-     * time than the write-sector savings returned (profiles/r02_pmc.json:
-     * the isolated residual-head stores also re-opened sectors). */
-    __shared__ uint32_t cur[NB];    /* global cursors for this block's chunk */
-    __shared__ uint32_t cnt4[WAVES_PER_BLOCK][NB]; /* per-wave-quarter counts,
-                                     * converted IN PLACE to per-wave staging
-                                     * cursors by the prefix (saves 8 KiB LDS
-                                     * => 3 blocks/CU) */
-    __shared__ uint32_t offs[NB];   /* per-supertile exclusive bin prefix     */
-    auto wofs = cnt4;
-    /* staged records carry their meta in .w (the payload's spare lane) and
-     * their destination is re-derived at flush by a 9-step binary search
-     * over offs[] — no per-record dest/meta staging arrays */
-    __shared__ uint4 s_rec[ST_RECORDS];
-    __shared__ uint32_t s_total;
-
-    for (int t = threadIdx.x; t < NB; t += BLOCK)
-        cur[t] = gofs[(int64_t)blockIdx.x * NB + t];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int64_t lo = blockIdx.x * chunk;
-    const int64_t hi = i64min(n, lo + chunk);
-    constexpr uint32_t SENT = 0xFFFFFFFFu;
-
-    for (int64_t st0 = lo; st0 < hi; st0 += st_rows) {
-        const int64_t st1 = i64min(hi, st0 + st_rows);
-        /* wave-quarter bounds (contiguous: wave order == row order) */
-        const int64_t q = ((st1 - st0) + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const int64_t w0 = i64min(st1, st0 + wave * q);
-        const int64_t w1 = i64min(st1, w0 + q);
-        /* pass A: expanded counts per (wave, bucket) */
-        for (int t = threadIdx.x; t < NB; t += BLOCK)
-            for (int w = 0; w < WAVES_PER_BLOCK; w++) cnt4[w][t] = 0;
-        __syncthreads();
-        for (int64_t i = w0 + lane; i < w1; i += 64) {
-            uint32_t m = 1;
-            if (wp.is_sliding) {
-                int32_t jm, mm;
-                row_windows(ts[i], wp, &jm, &mm);
-                m = (uint32_t)mm;
-            }
-            if (m) atomicAdd(&cnt4[wave][(uint32_t)kid[i] & (NB - 1)], m);
-        }
-        __syncthreads();
-        /* per-supertile prefix: offs (bin-major) + per-wave staging bases */
-        {
-            constexpr int PER = NB / BLOCK;
-            uint32_t tot[PER];
-            uint32_t s = 0;
-            for (int j = 0; j < PER; j++) {
-                int b = threadIdx.x * PER + j;
-                uint32_t t = 0;
-                for (int w = 0; w < WAVES_PER_BLOCK; w++) t += cnt4[w][b];
-                tot[j] = s;
-                s += t;
-            }
-            /* block scan over 256 partials */
-            __shared__ uint32_t scanbuf[BLOCK];
-            scanbuf[threadIdx.x] = s;
-            __syncthreads();
-            for (int o = 1; o < BLOCK; o <<= 1) {
-                uint32_t v = (threadIdx.x >= (unsigned)o) ? scanbuf[threadIdx.x - o] : 0;
-                __syncthreads();
-                scanbuf[threadIdx.x] += v;
-                __syncthreads();
-            }
-            uint32_t pre = threadIdx.x ? scanbuf[threadIdx.x - 1] : 0;
-            for (int j = 0; j < PER; j++) {
-                int b = threadIdx.x * PER + j;
-                uint32_t run = pre + tot[j];
-                offs[b] = run;
-                for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-                    uint32_t c = cnt4[w][b];
-                    wofs[w][b] = run; /* overlays cnt4 */
-                    run += c;
-                }
-            }
-            if (threadIdx.x == BLOCK - 1) s_total = scanbuf[BLOCK - 1];
-        }
-        __syncthreads();
-        /* pass B: ranked placement, PER-WAVE private cursors (no barriers) */
-        for (int64_t t0 = w0; t0 < w1; t0 += 64) {
-            const int64_t i = t0 + lane;
-            uint32_t bkt = SENT;
-            int32_t jmin = 0, m = 0;
-            uint32_t kv = 0, valid = 1;
-            double v = 0.0;
-            if (i < w1) {
-                kv = (uint32_t)kid[i];
-                v = vals[i];
-                if (validity) valid = (validity[i >> 3] >> (i & 7)) & 1u;
-                row_windows(ts[i], wp, &jmin, &m);
-                bkt = kv & (NB - 1);
-            }
-            uint32_t r = 0, wtot = 0;
-            int fl = lane;
-            if (!wp.is_sliding) {
-                /* m is 0/1: bit-ballot same-bucket mask (9+1 bits incl SENT) */
-                uint64_t same = ~0ULL;
-                for (int b = 0; b < 9; b++) {
-                    uint64_t bb = __ballot((bkt >> b) & 1);
-                    same &= ((bkt >> b) & 1) ? bb : ~bb;
-                }
-                {
-                    uint64_t bb = __ballot(bkt == SENT);
-                    same &= (bkt == SENT) ? bb : ~bb;
-                }
-                const uint64_t below =
-                    (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
-                r = (uint32_t)__popcll(same & below) - 1;
-                wtot = (uint32_t)__popcll(same);
-                fl = __ffsll((unsigned long long)same) - 1;
-            } else {
-                for (int j = 0; j < 64; j++) {
-                    uint32_t bj = (uint32_t)__builtin_amdgcn_readlane((int)bkt, j);
-                    uint32_t mj = (uint32_t)__builtin_amdgcn_readlane(m, j);
-                    if (bj == bkt) {
-                        if (j < lane) r += mj;
-                        wtot += mj;
-                        if (j < fl) fl = j;
-                    }
-                }
-            }
-            uint32_t base = 0;
-            {
-                uint32_t pre = 0;
-                if (lane == fl && bkt != SENT) {
-                    pre = wofs[wave][bkt];
-                    wofs[wave][bkt] = pre + wtot;
-                }
-                pre = (uint32_t)__shfl((int)pre, fl);
-                base = pre + r;
-            }
-            const uint32_t kloc = kv >> LOG_NB;
-            const uint64_t vb = (uint64_t)__double_as_longlong(v);
-            for (int jj = 0; jj < m; jj++) {
-                const uint32_t p = base + jj;
-                s_rec[p] = make_uint4(
-                    (uint32_t)vb, (uint32_t)(vb >> 32), (uint32_t)i,
-                    kloc | ((uint32_t)(jmin + jj) << META_WIDX_SHIFT)
-                         | (valid << META_VALID_SHIFT));
-            }
-        }
-        __syncthreads();
-        /* flush: bucket-major staging => coalesced run writes; the record's
-         * bin (and so its destination) falls out of a binary search over
-         * the bin prefix */
-        const uint32_t tot = s_total;
-        for (uint32_t p = threadIdx.x; p < tot; p += BLOCK) {
-            uint32_t b = 0;
-            for (int stp = NB >> 1; stp; stp >>= 1)
-                if (b + stp < NB && offs[b + stp] <= p) b += stp;
-            const uint32_t d = cur[b] + (p - offs[b]);
-            if (d < rec_limit) grec[d] = s_rec[p];
-            else dbg[0] = 1; /* bounds guard: flag, never corrupt */
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < NB; t += BLOCK) {
-            /* bin total = offs delta (cnt4 was overlaid by the cursors) */
-            uint32_t nxt = (t + 1 < NB) ? offs[t + 1] : s_total;
-            cur[t] += nxt - offs[t];
-        }
-        __syncthreads();
-    }
-}
-
 /* inclusive scan of one value per lane over the wave, in registers */
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, int lane) {
 #pragma unroll
@@ -1051,21 +868,39 @@ __device__ __forceinline__ void wave_quarter(T st0, T st1, int wave, T* w0,
     *w1 = *w0 + q < st1 ? *w0 + q : st1;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
+/* rows per supertile: ST_RECORDS, or the launch's st_rows when rows expand */
+__device__ __forceinline__ constexpr int64_t st_rows_of() { return ST_RECORDS; }
+__device__ __forceinline__ int64_t st_rows_of(int32_t st_rows) { return st_rows; }
+
+template <bool MULT, typename... SR>
+__global__ __launch_bounds__(BLOCK) void k_scatter_t(const int32_t* kid,
         const int64_t* ts, const double* vals, const uint8_t* validity,
         int64_t n, int64_t chunk, WinParams wp, const uint32_t* gofs,
-        uint4* grec, uint32_t rec_limit, uint32_t* dbg) {
-    /* k_scatter for the plain tumbling batch (every row lands in exactly one
-     * window, supertiles of ST_RECORDS rows): the same wave-quarter counts,
-     * bin prefix, ballot-ranked placement and bucket-major flush, so every
-     * record lands where k_scatter puts it — but each row's kid, ts, value
-     * and validity bit are read ONCE, into ST_SLOTS register slots per lane,
-     * counted and placed from there; the loads of supertile s+1 are issued
-     * before supertile s is counted, so their latency runs under its whole
-     * chain; and the chain is 4 block barriers (count | wave totals |
-     * cursors | placement) instead of 23: the chunk's global cursors live in
-     * their owner thread's registers, and each wave re-zeroes its own count
-     * row, which nobody else reads until the next prefix. */
+        uint4* grec, uint32_t rec_limit, uint32_t* dbg, SR... sr) {
+    /* LDS-staged stable partition. Each wave owns a CONTIGUOUS QUARTER of the
+     * supertile (wave order == row order), so staging cursors are per-wave
+     * private: no cross-wave serialization. Per supertile: wave-quarter
+     * counts, bin prefix, ranked placement into LDS, bucket-major flush, so
+     * adjacent lanes write adjacent global addresses (the direct form measured
+     * 6x write amplification — profiles/hbm_traffic.json). Each row's kid,
+     * ts, value and validity bit are read ONCE, into ST_SLOTS register slots
+     * per lane, counted and placed from there; the loads of supertile s+1 are
+     * issued before supertile s is counted, so their latency runs under its
+     * whole chain; and the chain is 4 block barriers (count | wave totals |
+     * cursors | placement): the chunk's global cursors live in their owner
+     * thread's registers, and each wave re-zeroes its own count row, which
+     * nobody else reads until the next prefix.
+     * MULT == false is the plain tumbling batch: every row lands in exactly
+     * one window, supertiles of ST_RECORDS rows. MULT == true (sliding and
+     * window-subrange launches) gives a row a multiplicity m of 0..expand-1:
+     * the supertile is st_rows rows (a launch argument that exists only
+     * here, so that st_rows * expand records fit the staging), a row counts
+     * m, ranks by the m of the lower lanes of its bucket, and stages m
+     * records with widx = jmin + jj. Nothing else differs, every difference
+     * is an if constexpr, and record order — so every destination in grec —
+     * is the same in both: bucket, then row, then window. */
+    static_assert(sizeof...(SR) == (MULT ? 1 : 0),
+                  "st_rows is passed exactly when MULT");
     __shared__ uint32_t cnt4[WAVES_PER_BLOCK][NB]; /* per-wave-quarter counts,
                                      * converted IN PLACE to per-wave staging
                                      * cursors by the prefix */
@@ -1087,6 +922,12 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
     for (int j = 0; j < PER; j++)
         cur[j] = gofs[(int64_t)blockIdx.x * NB + threadIdx.x * PER + j];
     for (int t = lane; t < NB; t += 64) cnt4[wave][t] = 0;
+    const int64_t st_rows = st_rows_of(sr...);
+    /* MULT is single-buffered: with the next supertile's rows held beside
+     * this one's it needs 172 VGPRs, over the 168 that 3 waves/SIMD allow, so
+     * it loads each supertile where it takes it over (as NX >= 2 does in
+     * k_regroup_t), and only the slots its wave quarter reaches */
+    constexpr bool PREFETCH = !MULT;
 
     /* the supertile's rows as loaded; rows past the quarter's end re-read the
      * chunk's last row (always in bounds) and are masked out below */
@@ -1096,9 +937,12 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
     uint32_t n_vb[ST_SLOTS];
     auto load_rows = [&](int64_t st0) {
         int64_t w0, w1;
-        wave_quarter(st0, i64min(hi, st0 + ST_RECORDS), wave, &w0, &w1);
+        wave_quarter(st0, i64min(hi, st0 + st_rows), wave, &w0, &w1);
 #pragma unroll
         for (int k = 0; k < ST_SLOTS; k++) {
+            if constexpr (MULT) {
+                if (w0 + k * 64 >= w1) break; /* wave-uniform */
+            }
             const int64_t i = i64min(w0 + k * 64 + lane, hi - 1);
             n_kid[k] = kid[i];
             n_ts[k] = ts[i];
@@ -1106,16 +950,23 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
             n_vb[k] = validity ? (uint32_t)validity[i >> 3] : 0xFFu;
         }
     };
-    load_rows(lo);
+    if constexpr (PREFETCH) load_rows(lo);
 
-    for (int64_t st0 = lo; st0 < hi; st0 += ST_RECORDS) {
+    for (int64_t st0 = lo; st0 < hi; st0 += st_rows) {
+        if constexpr (!PREFETCH) load_rows(st0);
         int64_t w0, w1;
-        wave_quarter(st0, i64min(hi, st0 + ST_RECORDS), wave, &w0, &w1);
-        /* this supertile's rows: bucket (SENT = no row), meta word, value */
+        wave_quarter(st0, i64min(hi, st0 + st_rows), wave, &w0, &w1);
+        /* this supertile's rows: bucket (SENT = no row), meta word (of the
+         * row's first window), value; MULT: the row's window count */
         uint32_t bk[ST_SLOTS], meta[ST_SLOTS];
         uint64_t vb[ST_SLOTS];
+        [[maybe_unused]] uint32_t mult[ST_SLOTS];
 #pragma unroll
         for (int k = 0; k < ST_SLOTS; k++) {
+            if constexpr (MULT) {
+                mult[k] = 0;
+                if (w0 + k * 64 >= w1) continue; /* wave-uniform: not loaded */
+            }
             const int64_t i = w0 + k * 64 + lane;
             const uint32_t kv = (uint32_t)n_kid[k];
             const uint32_t valid = (n_vb[k] >> (i & 7)) & 1u;
@@ -1125,12 +976,20 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
             meta[k] = (kv >> LOG_NB) | ((uint32_t)jmin << META_WIDX_SHIFT)
                     | (valid << META_VALID_SHIFT);
             vb[k] = (uint64_t)__double_as_longlong(n_val[k]);
+            if constexpr (MULT) mult[k] = i < w1 ? (uint32_t)m : 0u;
         }
-        if (st0 + ST_RECORDS < hi) load_rows(st0 + ST_RECORDS);
+        if constexpr (PREFETCH) {
+            if (st0 + st_rows < hi) load_rows(st0 + st_rows);
+        }
         /* counts per (wave, bucket), from registers */
 #pragma unroll
-        for (int k = 0; k < ST_SLOTS; k++)
-            if (bk[k] != SENT) atomicAdd(&cnt4[wave][bk[k]], 1u);
+        for (int k = 0; k < ST_SLOTS; k++) {
+            if constexpr (MULT) {
+                if (mult[k]) atomicAdd(&cnt4[wave][bk[k]], mult[k]);
+            } else {
+                if (bk[k] != SENT) atomicAdd(&cnt4[wave][bk[k]], 1u);
+            }
+        }
         __syncthreads();
         /* per-supertile prefix: offs (bin-major) + per-wave staging bases */
         uint32_t tot;
@@ -1167,31 +1026,60 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_tumbling(const int32_t* kid,
         for (int k = 0; k < ST_SLOTS; k++) {
             if (w0 + k * 64 >= w1) break; /* wave-uniform */
             const uint32_t bkt = bk[k];
-            /* bit-ballot same-bucket mask (9+1 bits incl SENT) */
-            uint64_t same = ~0ULL;
-            for (int b = 0; b < 9; b++) {
-                uint64_t bb = __ballot((bkt >> b) & 1);
-                same &= ((bkt >> b) & 1) ? bb : ~bb;
+            /* among the wave step's rows of this bucket: r = records of the
+             * lower lanes, wtot = records of all, fl = the lowest lane */
+            uint32_t r, wtot;
+            int fl;
+            if constexpr (MULT) {
+                /* weighted by each row's window count */
+                r = 0, wtot = 0, fl = lane;
+                for (int j = 0; j < 64; j++) {
+                    const uint32_t bj =
+                        (uint32_t)__builtin_amdgcn_readlane((int)bkt, j);
+                    const uint32_t mj =
+                        (uint32_t)__builtin_amdgcn_readlane((int)mult[k], j);
+                    if (bj == bkt) {
+                        if (j < lane) r += mj;
+                        wtot += mj;
+                        if (j < fl) fl = j;
+                    }
+                }
+            } else {
+                /* bit-ballot same-bucket mask (9+1 bits incl SENT) */
+                uint64_t same = ~0ULL;
+                for (int b = 0; b < 9; b++) {
+                    uint64_t bb = __ballot((bkt >> b) & 1);
+                    same &= ((bkt >> b) & 1) ? bb : ~bb;
+                }
+                {
+                    uint64_t bb = __ballot(bkt == SENT);
+                    same &= (bkt == SENT) ? bb : ~bb;
+                }
+                const uint64_t below =
+                    (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
+                r = (uint32_t)__popcll(same & below) - 1;
+                wtot = (uint32_t)__popcll(same);
+                fl = __ffsll((unsigned long long)same) - 1;
             }
-            {
-                uint64_t bb = __ballot(bkt == SENT);
-                same &= (bkt == SENT) ? bb : ~bb;
-            }
-            const uint64_t below =
-                (lane == 63) ? ~0ULL : ((1ULL << (lane + 1)) - 1);
-            const uint32_t r = (uint32_t)__popcll(same & below) - 1;
-            const uint32_t wtot = (uint32_t)__popcll(same);
-            const int fl = __ffsll((unsigned long long)same) - 1;
+            /* the lowest lane claims the step's records of the bucket */
             uint32_t pre = 0;
             if (lane == fl && bkt != SENT) {
                 pre = wofs[wave][bkt];
                 wofs[wave][bkt] = pre + wtot;
             }
             pre = (uint32_t)__shfl((int)pre, fl);
-            if (bkt != SENT)
-                s_rec[pre + r] = make_uint4(
-                    (uint32_t)vb[k], (uint32_t)(vb[k] >> 32),
-                    (uint32_t)(w0 + k * 64 + lane), meta[k]);
+            if constexpr (MULT) {
+                for (uint32_t jj = 0; jj < mult[k]; jj++)
+                    s_rec[pre + r + jj] = make_uint4(
+                        (uint32_t)vb[k], (uint32_t)(vb[k] >> 32),
+                        (uint32_t)(w0 + k * 64 + lane),
+                        meta[k] + (jj << META_WIDX_SHIFT)); /* jmin + jj */
+            } else {
+                if (bkt != SENT)
+                    s_rec[pre + r] = make_uint4(
+                        (uint32_t)vb[k], (uint32_t)(vb[k] >> 32),
+                        (uint32_t)(w0 + k * 64 + lane), meta[k]);
+            }
         }
         /* own count row back to zero for the next supertile (only this wave
          * touches it until the next prefix, two barriers on) */
@@ -1217,14 +1105,16 @@ void launch_scatter(hipStream_t s, const int32_t* d_kid, const int64_t* d_ts,
                     int64_t chunk, int C, int32_t st_rows, const WinParams& wp,
                     const uint32_t* d_gofs, uint4* d_grec, uint32_t rec_limit,
                     uint32_t* d_dbg) {
-    if (!wp.is_sliding && st_rows == ST_RECORDS)
-        hipLaunchKernelGGL(k_scatter_tumbling, dim3(C), dim3(BLOCK), 0, s,
+    if (!wp.is_sliding) {
+        assert(st_rows == ST_RECORDS); /* no expansion without sliding */
+        hipLaunchKernelGGL(k_scatter_t<false>, dim3(C), dim3(BLOCK), 0, s,
                            d_kid, d_ts, d_vals, d_validity, n, chunk, wp,
                            d_gofs, d_grec, rec_limit, d_dbg);
-    else
-        hipLaunchKernelGGL(k_scatter, dim3(C), dim3(BLOCK), 0, s, d_kid, d_ts,
-                           d_vals, d_validity, n, chunk, st_rows, wp, d_gofs,
-                           d_grec, rec_limit, d_dbg);
+    } else {
+        hipLaunchKernelGGL((k_scatter_t<true, int32_t>), dim3(C), dim3(BLOCK),
+                           0, s, d_kid, d_ts, d_vals, d_validity, n, chunk, wp,
+                           d_gofs, d_grec, rec_limit, d_dbg, st_rows);
+    }
 }
 
 /* ------------------------------------------------------------------ */
@@ -2011,7 +1901,6 @@ __global__ __launch_bounds__(BLOCK) void k_rscatter(const uint64_t* keys,
     /* stable per-block scatter: wave-quarters (wave order == element order)
      * with per-(wave,digit) counts -> private cursors */
     __shared__ uint32_t cnt4[WAVES_PER_BLOCK][RBINS]; /* overlaid to cursors */
-    __shared__ uint32_t scanbuf[BLOCK];
     const uint32_t nt = *counter;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -2039,7 +1928,6 @@ __global__ __launch_bounds__(BLOCK) void k_rscatter(const uint64_t* keys,
                 run += c;
             }
         }
-        (void)scanbuf;
     }
     __syncthreads();
     for (uint32_t t0 = w0; t0 < w1; t0 += 64) {
@@ -3342,7 +3230,7 @@ constexpr int MED_TILE = 2048;             /* rows per count/append block */
 constexpr int MED_RPT = MED_TILE / BLOCK;  /* rows one thread holds */
 
 /* The windows of this block's row tile: each thread's rows keep (first widx,
- * multiplicity) in registers — the same membership rule as k_hist/k_scatter
+ * multiplicity) in registers — the same membership rule as k_hist/k_scatter_t
  * (row_windows), multiplicity 0 for NULL rows — and the block's touched
  * widx range [*wlo, *wlo + *span) comes back through s_range. */
 __device__ __forceinline__ void med_tile_windows(

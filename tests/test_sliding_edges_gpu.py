@@ -1,6 +1,7 @@
-"""GPU tests of the sliding scatter (k_scatter) at its tile and window edges.
+"""GPU tests of the sliding scatter (k_scatter_t<true>) at its tile and window
+edges.
 
-k_scatter serves the sliding launches and the window-subrange splits; the
+k_scatter_t<true> serves the sliding launches and the window-subrange splits; the
 suite reached it only through workload-shaped streams whose slide divides the
 snap unit and whose row counts sit far from any supertile edge. Every case
 here is differential against tests/streamref.py (a row-list model, tied to
@@ -578,3 +579,107 @@ def test_device_push_i64_at_the_supertile_seams():
     got = run_device("i64", F64_SIX, 1000, 300, [batch])
     assert_exact(got, ref, "F64_SIX")
     assert ref["count"].sum() == expected_records(1000, 300, [batch])
+
+
+# ------------------------- 11. runtime supertile length over several chunks
+
+def subrange_multiplicity(ts, len_ms, slide_ms):
+    """Per subrange launch of the batch, each row's window count there."""
+    cover = cover_of(ts, len_ms, slide_ms)[1]
+    return [cover[:, a:a + SPLIT_WINDOWS].sum(axis=1)
+            for a in range(0, cover.shape[1], SPLIT_WINDOWS)]
+
+
+def test_short_last_supertiles_of_two_chunks():
+    n = 8193
+    expand, st = geometry(500, 100)
+    c, chunk = chunks_of(n)
+    assert (c, chunk, expand, st) == (2, 4097, 6, 341)
+    tail0, tail1 = chunk % st, (n - chunk) % st
+    assert (tail0, tail1) == (5, 4)
+    q = quarter_bounds(tail0)
+    assert [b - a for a, b in zip(q[:-1], q[1:])] == [2, 2, 1, 0]
+    rng = np.random.default_rng(1101)
+    ts = spread(rng, n, T0 + 137, 30000)
+    starts = cover_of(ts, 500, 100)[0]
+    assert 2 * SPLIT_WINDOWS >= len(starts) > SPLIT_WINDOWS
+    cut = int(starts[SPLIT_WINDOWS])      # the second subrange's first start
+    ts[chunk - 5:chunk - 2] = [cut - 50, cut + 50, cut + 450]
+    ids = np.array([0, 512, 1024, 1536, 1, 513, 1025], np.int64)
+    assert len(set((ids & 511).tolist())) == 2           # 7 keys, two buckets
+    k = rng.choice(ids, n)
+    m = subrange_multiplicity(ts, 500, 100)
+    assert len(m) == 2
+    assert {0, 1, 5} <= set(m[1][chunk - tail0:chunk].tolist())
+    batch = (ts, k, values("F64_VAR", rng, n))
+    stats = {}
+    _, ref = check("F64_VAR", 500, 100, [batch], dense=True, n_keys_hint=2048,
+                   stats=stats, max_open_windows=512)
+    assert stats["scatter"]["launches"] == 2 == stats["hist"]["launches"]
+    assert ref["count"].sum() == expected_records(500, 100, [batch])
+
+
+def test_tumbling_subranges_fill_all_slots():
+    n = 8193
+    c, chunk = chunks_of(n)
+    assert (c, chunk) == (2, 4097)
+    st = ST                  # tumbling: expand 1, a supertile of ST rows, and
+    assert -(-st // WAVES) == 8 * 64      # 8 wave steps per quarter
+    rng = np.random.default_rng(1102)
+    ts = spread(rng, n, T0, 300_000)
+    starts, cover = cover_of(ts, 1000, 0)
+    assert len(starts) == 300
+    assert (cover.sum(axis=1) == 1).all()
+    first = cover[:, :SPLIT_WINDOWS].any(axis=1)        # m = 1 in subrange 1
+    assert 0 < first[:64].sum() < 64, "one wave step, one subrange"
+    seams = [s for lo in (0, chunk) for s in range(lo + st, n, st)
+             if s < min(n, lo + chunk)]
+    assert seams == [2048, 4096, 6145] and seams[2] % 8 != 0
+    valid = (rng.random(n) > 0.3).astype(np.uint8)
+    for s in seams + [chunk]:
+        valid[s - 1:s + 2] = [1, 0, 1]
+    batch = (ts, rng.integers(0, 5, n).astype(np.int64),
+             values("F64_VAR", rng, n))
+    stats = {}
+    _, ref = check("F64_VAR", 1000, 0, [batch], [valid], stats=stats,
+                   max_open_windows=512)
+    # one scatter per subrange; hist counts the ingest's full-range pass too
+    assert stats["scatter"]["launches"] == 2 == stats["hist"]["launches"] - 1
+    assert ref["count"].sum() == int(valid.sum())
+
+
+def test_chunk_of_whole_supertiles():
+    expand, st = geometry(1000, 500)
+    assert (expand, st) == (3, 682)
+    n = 2 * 12 * st
+    c, chunk = chunks_of(n)
+    assert c == 2 and chunk % st == 0 and n < 2 * 8192
+    rng = np.random.default_rng(1103)
+    k = rng.integers(0, 9, n).astype(np.int64)
+    k[chunk - 1], k[chunk] = 100, 101      # the rows either side of the seam
+    batch = (spread(rng, n, T0 + 137, 1400), k, values("F64_VAR", rng, n))
+    stats = {}
+    _, ref = check("F64_VAR", 1000, 500, [batch], stats=stats)
+    assert stats["scatter"]["launches"] == 1 == stats["hist"]["launches"]
+    m = cover_of(batch[0], 1000, 500)[1].sum(axis=1)
+    for key, row in ((100, chunk - 1), (101, chunk)):
+        assert ref["count"][ref["key"] == key].sum() == m[row]
+    assert ref["count"].sum() == int(m.sum())
+
+
+def test_one_row_supertiles():
+    expand, st = geometry(2047, 1)
+    assert (expand, st) == (ST, 1)
+    assert quarter_bounds(st) == [0, 1, 1, 1, 1]         # three empty waves
+    rows = 70
+    assert chunks_of(rows) == (1, rows)
+    rng = np.random.default_rng(1104)
+    batch = (spread(rng, rows, T0 + 137, 50),
+             rng.integers(0, 5, rows).astype(np.int64),
+             values("F64_VAR", rng, rows))
+    starts = cover_of(batch[0], 2047, 1)[0]
+    stats = {}
+    _, ref = check("F64_VAR", 2047, 1, [batch], stats=stats,
+                   max_open_windows=4096)
+    assert stats["scatter"]["launches"] == -(-len(starts) // SPLIT_WINDOWS) > 1
+    assert ref["count"].sum() == rows * 2047

@@ -1,5 +1,5 @@
 """GPU tests of the single-read supertile loop in the tumbling scatter
-(k_scatter_tumbling) and in the regroup/fold kernels: every row or record is
+(k_scatter_t<false>) and in the regroup/fold kernels: every row or record is
 held in registers from its one load to its placement, the bin prefix is a wave
 scan, and the next supertile's loads are in flight under the current one.
 
